@@ -46,6 +46,8 @@ BATCH, PHONEMES, FRAMES_PAD, DUR = 32, 85, 512, 6      # 85 phonemes x 6 frames 
 N_STEPS = 4
 FP32_MFMA_PEAK_TFLOPS = 157.3                           # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 peak
 HBM_PEAK_GBS = 8000.0
+DEVICE_SEED = 4321                                      # the device generator the in-step noise is drawn from (+ rank)
+DUMP_LIMIT_BYTES = 64 << 20                             # --dump-outputs writes at most this much
 
 
 def log(*a):
@@ -494,6 +496,28 @@ def config_blocks(device, voc, extras):
     return out
 
 
+def dump_outputs(out_dir, arrays):
+    """Write each array as <out_dir>/<name>.npy: floating arrays as float32, integer arrays as float64 (exact for the
+    lengths and indices dumped here).  Arrays past DUMP_LIMIT_BYTES are replaced by a fixed, seeded sample of their
+    flattened elements (<name>.npy) and the sample's flat indices (<name>_index.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        a = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+        if total + a.nbytes > DUMP_LIMIT_BYTES:
+            room = (DUMP_LIMIT_BYTES - total) // (2 * 8)        # value + index, at most 8 bytes each
+            if room <= 0:
+                raise ValueError(f"--dump-outputs: no room left for {name!r} within {DUMP_LIMIT_BYTES} bytes")
+            idx = np.sort(np.random.RandomState(0).choice(a.size, size=min(room, a.size), replace=False)).astype(np.float64)
+            a = a.reshape(-1)[idx.astype(np.int64)]
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx)
+            total += idx.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    return total
+
+
 def self_launch(args, argv):
     """`python bench.py --gpus N` with N > 1 and no rendezvous in the environment starts the N ranks ITSELF (one process per GPU
     through torch.distributed.run on 127.0.0.1) and returns their exit code; under torch.distributed.run (WORLD_SIZE set: the
@@ -563,7 +587,11 @@ def main():
     ap.add_argument("--unfused", action="store_true", help="three-launch residual block (A/B)")
     ap.add_argument("--per-layer", action="store_true", help="one fused launch per residual layer instead of the persistent stack (A/B)")
     ap.add_argument("--tile", type=int, default=0, help="frames per workgroup of the fused residual block (tuning)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (mel, lengths, durations, pitch, energy) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rc = self_launch(args, sys.argv[1:])
     if rc is not None:
@@ -576,6 +604,7 @@ def main():
     quiet_stdout()
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
+    torch.cuda.manual_seed(DEVICE_SEED + rank)      # the in-step noise: the same draws from run to run (torch's default seed is not fixed)
     if world > 1:
         torch.distributed.init_process_group("nccl", device_id=device)
         world = torch.distributed.get_world_size()       # n_gpus in the JSON line = the ranks RCCL actually joined
@@ -621,6 +650,10 @@ def main():
         if gather:
             state["pending"] = shard.allgather_mels_async(mel, out["mel_lens"], force=True)
         state["mel"], state["mel_len"] = mel, out["mel_lens"]
+        # the text side's per-utterance outputs (small; not cond_ct and its factors, so no step keeps the previous one's buffers alive)
+        state["text_out"] = {"log_d_predictions": out["log_d_predictions"], "d_rounded": out["d_rounded"], "mel2ph": out["mel2ph"],
+                             "f0_denorm": out["p_predictions"]["f0_denorm"], "p_idx": out["p_predictions"]["p_idx"],
+                             "e_predictions": out["e_predictions"], "e_idx": out["e_idx"]}
 
     step()
     flush()
@@ -644,6 +677,11 @@ def main():
                before=lambda: _lib.check(lib.cmtts_profile_begin(args.steps * N_STEPS * cfg.res_layers, stride)))
     tot_ms, n_l = C.c_double(), C.c_int()
     _lib.check(lib.cmtts_profile_end(C.byref(tot_ms), C.byref(n_l)))
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the mels (every rank's, collated, when they are gathered) and the text side's
+        # per-utterance outputs of this rank's batch
+        dump_outputs(args.dump_outputs, dict({"mel": state["gathered"] if gather else state["mel"],
+                                              "mel_lens": state["gathered_len"] if gather else state["mel_len"]}, **state["text_out"]))
     frames_total = frames_rank * world * args.steps
     value = frames_total / dt
     ms_per_step = dt / args.steps * 1e3

@@ -20,9 +20,18 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, q):
+def _join_gloo(rank, world, port):
+    """Join the CPU (gloo) group as `rank`.  These ranks never use a GPU, but torch.distributed asks for the machine's accelerator
+    (init_process_group, barrier), and on a GPU host that query brings up the HIP runtime: every rank would then hold the device
+    open (eight in test_configs3_recipe_world8).  The queries are answered with "no accelerator" before the group is joined."""
+    torch.accelerator.current_accelerator = lambda check_available=False: None
+    torch._C._get_accelerator = lambda: torch.device("cpu")
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
+
+
+def _worker(rank, world, port, q):
+    _join_gloo(rank, world, port)
     Bl, T, M = 3, 16, 80
     g = torch.Generator().manual_seed(100 + rank)
     mel = torch.randn(Bl, T, M, generator=g)
@@ -112,8 +121,7 @@ def _fake_synth(idx, bucket):
 
 
 def _worker_plan(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    _join_gloo(rank, world, port)
     plan = shard.plan_shards(FRAMES, world)
     gathered = {}
     for bucket, ranks in plan.items():
@@ -184,8 +192,7 @@ def _mel_of(idx, n, bucket, M):
 
 
 def _worker_cfg3(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    _join_gloo(rank, world, port)
     frames = _cfg3_lengths(world)
     plan = shard.plan_shards(frames, world)
     M = 80
@@ -297,8 +304,7 @@ class _StandInHost:
 
 
 def _worker_extras(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    _join_gloo(rank, world, port)
     import argparse
     import bench
     torch.cuda.synchronize = lambda *a, **k: None           # this process has no GPU: the stand-ins compute on the host
