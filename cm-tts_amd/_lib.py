@@ -55,6 +55,9 @@ SIGNATURES = {
     "cmtts_frame_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_frame_forward_sub": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_frame_forward_sub_t": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cmtts_text_state_record_bytes": (_sz, [_vp, _i]),
+    "cmtts_text_state_pack": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "cmtts_text_state_unpack": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
     "cmtts_length_regulate": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "cmtts_denoiser_workspace_bytes": (_sz, [_vp, _i, _i]),
     "cmtts_denoiser_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
@@ -92,13 +95,14 @@ SIGNATURES = {
     "cmtts_allgather_mels": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_allgather_pcm_workspace_bytes": (_sz, [_i, _i, _i64]),
     "cmtts_allgather_pcm": (_i, [_vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "cmtts_exchange_records": (_i, [_vp, _i, _vp, C.POINTER(_i64), _vp, C.POINTER(_i64), _sz, _vp]),
     "cmtts_transpose": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "cmtts_pack_conv_weight": (_i, [_vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_i)]),
     "cmtts_free_device": (None, [_vp]),
     "cmtts_conv1d": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
-ABI_VERSION = 5          # include/cmtts_hip.h: CMTTS_ABI_VERSION
+ABI_VERSION = 6          # include/cmtts_hip.h: CMTTS_ABI_VERSION
 _lib = None
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cmtts_hip.h")
 

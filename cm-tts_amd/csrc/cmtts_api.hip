@@ -23,6 +23,7 @@
 #include "resblock_pair.h"
 #include "inproj.h"
 #include "attention.h"
+#include "text_state.h"
 
 namespace {
 
@@ -2056,6 +2057,78 @@ int cmtts_frame_forward_sub_t(cmtts_model* m, const void* text_ws, int B_all, in
     if (g_cwt_in_phoneme) k_lr_gather_add(tw.out1, mel2ph, Lp, p_idx, m->pitch_emb, cond_ct, B, H, T, s);
     else k_gather_add(w.xlr, p_idx, m->pitch_emb, cond_ct, B, H, T, s);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- per-utterance text-side state records (text_state.hip): the regions of a text workspace that cmtts_frame_forward_sub reads —
+// out1 [H][Lp], h128 [cwt_hidden][Lp], spk [H] (fp32), cum [L] (int32) — behind a 64-byte header, each region 16-byte aligned.
+namespace {
+struct TextStateLayout {
+    long off[TEXT_STATE_MAX_REGIONS], bytes[TEXT_STATE_MAX_REGIONS], stride[TEXT_STATE_MAX_REGIONS];
+    long rec_bytes;
+};
+TextStateLayout text_state_layout(const cmtts_config& c, int L) {
+    const int Lp = round_up(L, 4);
+    TextStateLayout t;
+    t.bytes[0] = (long)c.hidden * Lp * 4;       // out1
+    t.bytes[1] = (long)c.cwt_hidden * Lp * 4;   // h128
+    t.bytes[2] = (long)c.hidden * 4;            // spk
+    t.bytes[3] = (long)L * 4;                   // cum
+    long off = TEXT_STATE_HEADER_BYTES;
+    for (int g = 0; g < TEXT_STATE_MAX_REGIONS; ++g) {
+        t.stride[g] = t.bytes[g];               // per-utterance stride in the workspace: the regions are [B][...] slabs
+        t.off[g] = off;
+        off += (t.bytes[g] + 15) / 16 * 16;
+    }
+    t.rec_bytes = off;
+    return t;
+}
+TextStateCopy text_state_args(const cmtts_config& c, void* ws, int B_all, int L, void* records, int n, int unpack) {
+    const TextStateLayout t = text_state_layout(c, L);
+    TextWs tw = carve_text(c, B_all, L, ws);
+    char* base[TEXT_STATE_MAX_REGIONS] = {(char*)tw.out1, (char*)tw.h128, (char*)tw.spk, (char*)tw.cum};
+    TextStateCopy a;
+    memset(&a, 0, sizeof(a));
+    int chunks = 0;
+    for (int g = 0; g < TEXT_STATE_MAX_REGIONS; ++g) {
+        TextStateRegion& R = a.reg[g];
+        R.ws = base[g]; R.ws_stride = t.stride[g]; R.rec_off = t.off[g]; R.bytes = t.bytes[g];
+        R.vec16 = ((uintptr_t)R.ws % 16 == 0 && R.ws_stride % 16 == 0 && R.bytes % 16 == 0 && (uintptr_t)records % 16 == 0) ? 1 : 0;
+        R.chunk0 = chunks;
+        chunks += (int)((R.bytes + TEXT_STATE_CHUNK - 1) / TEXT_STATE_CHUNK);
+    }
+    a.n_regions = TEXT_STATE_MAX_REGIONS; a.n_chunks = chunks; a.unpack = unpack;
+    a.n = n; a.B_all = B_all; a.L_all = L; a.hidden = c.hidden; a.cwt_hidden = c.cwt_hidden;
+    a.rec = (char*)records; a.rec_bytes = t.rec_bytes;
+    a.cum = tw.cum;
+    return a;
+}
+}  // namespace
+
+size_t cmtts_text_state_record_bytes(const cmtts_model* m, int L_all) {
+    if (!m || L_all <= 0) return 0;
+    return (size_t)text_state_layout(m->cfg, L_all).rec_bytes;
+}
+
+int cmtts_text_state_pack(cmtts_model* m, const void* text_ws, int B_all, int L_all, const int32_t* rows, int n, const int64_t* global_idx,
+                          const int64_t* src_lens, void* records, void* stream) {
+    if (!m || !m->finalized) return fail(CMTTS_E_INVALID, "model not finalized");
+    if (!text_ws || !records || (n > 0 && !rows) || B_all <= 0 || L_all <= 0 || n < 0)
+        return fail(CMTTS_E_INVALID, "cmtts_text_state_pack: bad argument");
+    if ((uintptr_t)records % 16) return fail(CMTTS_E_INVALID, "cmtts_text_state_pack: records must be 16-byte aligned");
+    TextStateCopy a = text_state_args(m->cfg, const_cast<void*>(text_ws), B_all, L_all, records, n, 0);
+    a.rows = rows; a.index = global_idx; a.src_lens = src_lens;
+    if (cmtts_launch_text_state_copy(&a, stream) != 0) return fail(CMTTS_E_HIP, "text-state pack launch failed");
+    return 0;
+}
+
+int cmtts_text_state_unpack(cmtts_model* m, const void* records, int n, int L_all, void* text_ws, size_t text_ws_bytes, void* stream) {
+    if (!m || !m->finalized) return fail(CMTTS_E_INVALID, "model not finalized");
+    if (!text_ws || !records || n <= 0 || L_all <= 0) return fail(CMTTS_E_INVALID, "cmtts_text_state_unpack: bad argument");
+    if ((uintptr_t)records % 16) return fail(CMTTS_E_INVALID, "cmtts_text_state_unpack: records must be 16-byte aligned");
+    if (text_ws_bytes < carve_text(m->cfg, n, L_all, nullptr).bytes) return fail(CMTTS_E_WORKSPACE, "text workspace too small");
+    TextStateCopy a = text_state_args(m->cfg, text_ws, n, L_all, const_cast<void*>(records), n, 1);
+    if (cmtts_launch_text_state_copy(&a, stream) != 0) return fail(CMTTS_E_HIP, "text-state unpack launch failed");
     return 0;
 }
 

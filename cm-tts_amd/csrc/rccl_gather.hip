@@ -17,6 +17,8 @@ typedef int (*fn_get_unique_id)(void*);
 typedef int (*fn_comm_destroy)(void*);
 typedef int (*fn_all_gather)(const void*, void*, size_t, int, void*, hipStream_t);
 typedef const char* (*fn_error_string)(int);
+typedef int (*fn_send_recv)(void*, size_t, int, int, void*, hipStream_t);      // ncclSend (const buffer) / ncclRecv
+typedef int (*fn_group)(void);
 
 struct NcclUniqueId { char internal[128]; };        // ncclUniqueId: 128 opaque bytes, passed BY VALUE to ncclCommInitRank
 typedef int (*fn_comm_init_rank_v)(void**, int, NcclUniqueId, int);
@@ -28,6 +30,8 @@ struct Rccl {
     fn_comm_destroy comm_destroy = nullptr;
     fn_all_gather all_gather = nullptr;
     fn_error_string error_string = nullptr;
+    fn_send_recv send = nullptr, recv = nullptr;       // point-to-point (cmtts_exchange_records); optional
+    fn_group group_start = nullptr, group_end = nullptr;
     bool tried = false;
 } g_rccl;
 
@@ -52,6 +56,10 @@ bool rccl_open() {
     g_rccl.comm_destroy = (fn_comm_destroy)dlsym(g_rccl.h, "ncclCommDestroy");
     g_rccl.all_gather = (fn_all_gather)dlsym(g_rccl.h, "ncclAllGather");
     g_rccl.error_string = (fn_error_string)dlsym(g_rccl.h, "ncclGetErrorString");
+    g_rccl.send = (fn_send_recv)dlsym(g_rccl.h, "ncclSend");
+    g_rccl.recv = (fn_send_recv)dlsym(g_rccl.h, "ncclRecv");
+    g_rccl.group_start = (fn_group)dlsym(g_rccl.h, "ncclGroupStart");
+    g_rccl.group_end = (fn_group)dlsym(g_rccl.h, "ncclGroupEnd");
     if (!g_rccl.get_unique_id || !g_rccl.comm_init_rank || !g_rccl.comm_destroy || !g_rccl.all_gather) {
         g_rccl.h = nullptr;
         return false;
@@ -178,6 +186,47 @@ int cmtts_allgather_pcm(void* comm, int world, const int16_t* pcm, const int64_t
     }
     hipLaunchKernelGGL(unpack_pcm_kernel, dim3((unsigned)((N + 255) / 256), world * Bl), dim3(256), 0, s, gathered, out_pcm, out_len, N, rowp);
     if (hipGetLastError() != hipSuccess) return cmtts_internal_fail(CMTTS_E_HIP, "pcm all-gather pack/unpack launch failed");
+    return 0;
+}
+
+// Text-state records to the ranks the length plan gives them (the hand-off of a sharded synthesis, cmtts_text_state_pack): rank r sends
+// send_counts[p] consecutive records to rank p (in rank order from `send`) and receives recv_counts[p] records from rank p (in rank order
+// into `recv`) — ONE grouped ncclSend / ncclRecv round with uneven splits, bytes on the wire (ncclInt8).  Counts are HOST int64 [world].
+// Without a communicator (world 1) the records are copied on `stream`.
+int cmtts_exchange_records(void* comm, int world, const void* send, const int64_t* send_counts, void* recv, const int64_t* recv_counts,
+                           size_t record_bytes, void* stream) {
+    if (world < 1 || !send_counts || !recv_counts || record_bytes == 0)
+        return cmtts_internal_fail(CMTTS_E_INVALID, "cmtts_exchange_records: bad argument");
+    if (world > 1 && !comm) return cmtts_internal_fail(CMTTS_E_INVALID, "cmtts_exchange_records: a communicator is required for world > 1");
+    size_t ns = 0, nr = 0;
+    for (int p = 0; p < world; ++p) {
+        if (send_counts[p] < 0 || recv_counts[p] < 0) return cmtts_internal_fail(CMTTS_E_INVALID, "cmtts_exchange_records: negative count");
+        ns += (size_t)send_counts[p];
+        nr += (size_t)recv_counts[p];
+    }
+    if ((ns && !send) || (nr && !recv)) return cmtts_internal_fail(CMTTS_E_INVALID, "cmtts_exchange_records: null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    if (!comm) {
+        if (ns != nr) return cmtts_internal_fail(CMTTS_E_INVALID, "cmtts_exchange_records: one rank sends what it receives");
+        if (ns && hipMemcpyAsync(recv, send, ns * record_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return cmtts_internal_fail(CMTTS_E_HIP, "cmtts_exchange_records: copy failed");
+        return 0;
+    }
+    if (!rccl_open()) return cmtts_internal_fail(CMTTS_E_UNSUPPORTED, "librccl.so could not be opened (dlopen)");
+    if (!g_rccl.send || !g_rccl.recv || !g_rccl.group_start || !g_rccl.group_end)
+        return cmtts_internal_fail(CMTTS_E_UNSUPPORTED, "librccl.so lacks ncclSend / ncclRecv / ncclGroupStart / ncclGroupEnd");
+    int r = g_rccl.group_start();
+    size_t so = 0, ro = 0;
+    for (int p = 0; p < world && r == 0; ++p) {
+        const size_t sb = (size_t)send_counts[p] * record_bytes, rb = (size_t)recv_counts[p] * record_bytes;
+        if (sb) r = g_rccl.send(const_cast<char*>((const char*)send + so), sb, /*ncclInt8*/ 0, p, comm, s);
+        if (r == 0 && rb) r = g_rccl.recv((char*)recv + ro, rb, /*ncclInt8*/ 0, p, comm, s);
+        so += sb;
+        ro += rb;
+    }
+    const int re = g_rccl.group_end();
+    if (r == 0) r = re;
+    if (r != 0) return cmtts_internal_fail(CMTTS_E_HIP, g_rccl.error_string ? g_rccl.error_string(r) : "ncclSend / ncclRecv failed");
     return 0;
 }
 

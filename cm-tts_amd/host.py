@@ -1315,3 +1315,140 @@ def get_vocoder(config, device, root="."):
     vocoder.eval()
     vocoder.remove_weight_norm()
     return vocoder
+
+
+# ---- a batch that starts from TEXT, sharded over the ranks of a process group by predicted mel length (shard.two_phase): the text
+# side of each rank's slice, its per-utterance state packed into records (cmtts_text_state_pack), the lengths agreed, the records moved
+# to the ranks the plan gives them, unpacked into one text workspace per bucket (cmtts_text_state_unpack) and the frame side + sampler
+# of every bucket group run there (one cmtts_sample_ragged call for the rank's groups, like BucketedSynthesizer).
+
+def utterance_noise(seed, index, n_noise, T, n_mels, device):
+    """The sampler's noise [n_noise, 1, T, n_mels] of ONE utterance, drawn from a generator seeded by (seed, global utterance index):
+    an utterance gets the same noise whatever the world size and whichever rank computes it."""
+    g = torch.Generator(device=device)
+    g.manual_seed((int(seed) * 1000003 + int(index)) % (1 << 63))
+    return torch.randn(n_noise, 1, int(T), int(n_mels), generator=g, device=device)
+
+
+def text_state_records(model: CMTotalTTS, texts, src_lens, lo, hi, spker_embeds=None, speakers=None, d_control=1.0):
+    """Text side of utterances [lo, hi) of a batch padded to L_all = texts.shape[1] phonemes (the reference's batch padding,
+    cmtts_text_forward), packed into text-state records.  Returns (records uint8 [hi - lo, R], mel_len int64 [hi - lo]) on the
+    model's device."""
+    o = model
+    o._require()
+    cfg, lib, dev = o.config, o.lib, o.device
+    L = int(texts.shape[1])
+    R = lib.cmtts_text_state_record_bytes(o._h, L)
+    n = hi - lo
+    if n <= 0:
+        return torch.empty(0, R, dtype=torch.uint8, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
+    tx = _i64(texts[lo:hi], dev)
+    sl = _i64(src_lens[lo:hi], dev)
+    table = cfg.multi_speaker and cfg.n_speaker > 0
+    spk_in = _f32(spker_embeds[lo:hi], dev) if (cfg.multi_speaker and not table) else None
+    ids = _i64(speakers[lo:hi], dev) if table else None
+    if cfg.multi_speaker and not table and spker_embeds is None:
+        raise AssertionError("Speaker embedding should not be None")
+    if table:
+        if speakers is None:
+            raise AssertionError("speakers (ids into the speaker_emb table) should not be None")
+        if int(ids.min()) < 0 or int(ids.max()) >= cfg.n_speaker:
+            raise IndexError("index out of range in self")
+    with torch.cuda.device(dev):
+        mel_len = torch.empty(n, dtype=torch.int64, device=dev)
+        nb = lib.cmtts_text_workspace_bytes(o._h, n, L)
+        tws = o._ws.get("text_sharded", nb, dev)
+        _lib.check(lib.cmtts_text_forward(o._h, _ptr(tx), _ptr(sl), _ptr(spk_in), _ptr(ids), n, L, float(d_control),
+                                          None, None, _ptr(mel_len), None, None, None, None, _ptr(tws), nb, _stream()))
+        rows = torch.arange(n, dtype=torch.int32, device=dev)
+        gidx = torch.arange(lo, hi, dtype=torch.int64, device=dev)
+        records = torch.empty(n, R, dtype=torch.uint8, device=dev)
+        _lib.check(lib.cmtts_text_state_pack(o._h, _ptr(tws), n, L, _ptr(rows), n, _ptr(gidx), _ptr(sl), _ptr(records), _stream()))
+    return records, mel_len
+
+
+def frame_side_from_records(model: CMTotalTTS, groups, L_all, n_steps=4, seed=0, tail_frames=16, details=None):
+    """groups: [(bucket, records uint8 [n, R], utterance ids [n], planned lengths [n])] (shard.two_phase).  Every group's records are
+    unpacked into a text workspace of its own, its frame side runs with T = bucket, and ONE cmtts_sample_ragged call samples all
+    groups (each utterance trimmed to its planned length + tail_frames) with utterance_noise(seed, id).  Returns [(mel [n, bucket, 80],
+    mel_len int64 [n])]; `details` (a list) receives one {"mel2ph", "p_idx", "ids"} per group."""
+    from . import shard
+    cfg, lib, dev = model.config, model.lib, model.device
+    n_noise = 1 if n_steps == 1 else n_steps + 1
+    lay = shard.text_state_layout(cfg.hidden, cfg.cwt_hidden, L_all)
+    p1_ld = (L_all + 3) // 4 * 4
+    use_p1 = getattr(model, "_precision_mode", 0) == 0 and model._cond_factors
+    sample_groups, lens = [], []
+    with torch.cuda.device(dev):
+        f = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
+        for k, (bucket, rec, ids, planned) in enumerate(groups):
+            n, T = len(ids), int(bucket)
+            rec = rec.to(dev).contiguous()
+            nb = lib.cmtts_text_workspace_bytes(model._h, n, L_all)
+            tws = model._ws.get(("text_unpacked", k), nb, dev)
+            _lib.check(lib.cmtts_text_state_unpack(model._h, _ptr(rec), n, L_all, _ptr(tws), nb, _stream()))
+            cond_ct = f(n, cfg.hidden, T)
+            mel2ph = torch.empty(n, T, dtype=torch.int64, device=dev)
+            p_idx = torch.empty(n, T, dtype=torch.int64, device=dev)
+            p1 = f(n, cfg.res_layers * cfg.res_channels, p1_ld) if use_p1 else None
+            p1t = None if p1 is None else f(n, cfg.res_layers, p1_ld, cfg.res_channels)
+            nf = lib.cmtts_frame_workspace_bytes(model._h, n, T)
+            fws = model._ws.get(("frame_unpacked", k), nf, dev)
+            _lib.check(lib.cmtts_frame_forward_sub_t(model._h, _ptr(tws), n, L_all, 0, n, T, _ptr(cond_ct), _ptr(mel2ph), None, None,
+                                                     _ptr(p_idx), None, _ptr(p1), _ptr(p1t), _ptr(fws), nf, _stream()))
+            factors = None if p1 is None else CondFactors(p1, p1_ld, L_all, mel2ph, p_idx, cond_ct, p1t)
+            spk = shard.text_state_region(rec, lay, "spk") if cfg.multi_speaker else None
+            noise = torch.stack([utterance_noise(seed, i, n_noise, T, cfg.n_mels, dev) for i in ids], 1)
+            sample_groups.append((cond_ct, spk, noise, [int(t) for t in planned], factors))
+            lens.append(torch.tensor([int(t) for t in planned], dtype=torch.int64, device=dev))
+            if details is not None:
+                details.append({"mel2ph": mel2ph, "p_idx": p_idx, "ids": list(ids)})
+        mels = sample_ragged(model, sample_groups, n_steps, tail_frames)
+    return list(zip(mels, lens))
+
+
+def synthesize_sharded(model: CMTotalTTS, texts, src_lens, spker_embeds=None, speakers=None, n_steps=4, group=None, seed=0,
+                       buckets=None, vocoder=None, d_control=1.0, p_control=1.0, e_control=1.0, tail_frames=16, max_wav_value=32768.0):
+    """A batch of texts (synthesize.py batch mode: texts int64 [B, L], src_lens [B], the same on every rank) over the ranks of
+    `group` (torch.distributed; none initialised = one rank): text side of this rank's slice (shard.shard_range), lengths agreed,
+    text-state records moved to the ranks of the agreed plan_shards(mel_len) (shard.two_phase), frame side and sampler per bucket,
+    the mels of every rank all-gathered once.  An utterance longer than the largest bucket is truncated to it and reported.
+    Noise is drawn per utterance from (seed, global index) (utterance_noise): results do not depend on the world size.
+    Returns {"mels": [mel [len_i, 80]] in input order (every rank), "mel_len": the predicted lengths, "truncated": indices,
+    "plan": the plan; with `vocoder`: "wavs": [int16 [len_i * 256]] (shard.allgather_pcm per bucket)}."""
+    from . import shard
+    if buckets is None:
+        buckets = shard.FRAME_BUCKETS
+    model._require()
+    _note_process_group(model.lib)
+    texts = torch.as_tensor(texts)
+    src_lens = torch.as_tensor(src_lens)
+    L_all = int(src_lens.max())                       # the reference's batch padding: the longest utterance of the batch
+    texts = texts[:, :L_all]
+    n_items = int(texts.shape[0])
+    vc = None
+    if p_control != 1.0 or e_control != 1.0:
+        vc = _lib.VarianceControlsStruct(p_control=float(p_control), e_control=float(e_control))
+        _lib.check(model.lib.cmtts_set_variance_controls(model._h, C.byref(vc)))
+    try:
+        res = shard.two_phase(
+            n_items,
+            lambda lo, hi: text_state_records(model, texts, src_lens, lo, hi, spker_embeds, speakers, d_control),
+            lambda groups: frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames),
+            group=group, buckets=buckets)
+        if vocoder is not None:
+            wavs = [None] * n_items
+            for b, (mel, mel_len) in sorted(res["local"].items()):
+                pcm = vocoder_infer_device(mel.transpose(1, 2).contiguous(), vocoder, max_wav_value)
+                hop = pcm.shape[1] // mel.shape[1]
+                all_pcm, all_len = shard.allgather_pcm(pcm, mel_len * hop, group)
+                for row, i in enumerate(i for r in res["plan"][b] for i in r):
+                    if i >= 0:
+                        wavs[i] = all_pcm[row, :int(all_len[row])]
+            res["wavs"] = wavs
+    finally:
+        if vc is not None:
+            model.lib.cmtts_set_variance_controls(model._h, None)
+            torch.cuda.current_stream(model.device).synchronize()
+    check_async_error()
+    return res

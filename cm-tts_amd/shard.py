@@ -214,3 +214,164 @@ def allgather_buckets(mels, group=None, force: bool = False):
         res[b] = unpack_mels(blk, T, M)
         off += n
     return res
+
+
+# ---- sharding a batch that starts from TEXT (two phases).  Frame counts exist only after the duration predictor
+# (model/modules.py:369-376, synthesize.py:102-109), so: every rank runs the text side of its contiguous slice (shard_range) and packs
+# each utterance's text-side state into a fixed-size record (cmtts_text_state_pack); ONE all-gather of the int32 mel_len agrees on the
+# lengths and every rank computes the same plan_shards; each record moves to the rank that plan gives it (one all-to-all with uneven
+# splits: only what each rank needs); every rank runs the frame side of its buckets on the records (cmtts_text_state_unpack) and the
+# mels go through the existing all-gather (allgather_buckets).  The length and record exchanges are control traffic in front of
+# the data path's one all-gather of mels.
+
+TEXT_STATE_LAYOUT = 0x54530001
+TEXT_STATE_HEADER_BYTES = 64
+TEXT_STATE_REGIONS = ("out1", "h128", "spk", "cum")
+
+
+def text_state_layout(hidden: int, cwt_hidden: int, L_all: int):
+    """Byte layout of one text-state record (include/cmtts_hip.h, cmtts_text_state_*): {region: (offset, bytes)} and
+    "record_bytes".  out1 fp32 [hidden][Lp], h128 fp32 [cwt_hidden][Lp], spk fp32 [hidden], cum int32 [L_all] (Lp = L_all rounded
+    up to 4), each 16-byte aligned behind the 64-byte header."""
+    Lp = (L_all + 3) // 4 * 4
+    sizes = {"out1": hidden * Lp * 4, "h128": cwt_hidden * Lp * 4, "spk": hidden * 4, "cum": L_all * 4}
+    out, off = {}, TEXT_STATE_HEADER_BYTES
+    for r in TEXT_STATE_REGIONS:
+        out[r] = (off, sizes[r])
+        off += (sizes[r] + 15) // 16 * 16
+    out["record_bytes"] = off
+    return out
+
+
+def text_state_header(records: torch.Tensor):
+    """records uint8 [n, record_bytes] -> {"index", "mel_len" int64 [n], "src_len", "layout", "L_all" int32 [n]} (any device)."""
+    h = records[:, :TEXT_STATE_HEADER_BYTES].contiguous()
+    q, w = h.view(torch.int64), h.view(torch.int32)
+    return {"index": q[:, 0], "mel_len": q[:, 1], "src_len": w[:, 4], "layout": w[:, 5], "L_all": w[:, 6]}
+
+
+def text_state_region(records: torch.Tensor, layout, name: str, dtype=torch.float32) -> torch.Tensor:
+    """One region of every record as a [n, elements] tensor (a copy)."""
+    off, nb = layout[name]
+    return records[:, off:off + nb].contiguous().view(dtype)
+
+
+def planned_lengths(mel_len: Sequence[int], buckets: Sequence[int] = FRAME_BUCKETS):
+    """Frame counts the plan uses: an utterance longer than the largest bucket is truncated to it (and reported) instead of
+    failing the batch.  Returns (lengths, indices of the truncated utterances)."""
+    cap = int(buckets[-1])
+    lens = [min(int(t), cap) for t in mel_len]
+    return lens, [i for i, t in enumerate(mel_len) if int(t) > cap]
+
+
+def route_records(plan, n_items: int, world: int):
+    """plan (plan_shards) -> (slots, need).  slots: {bucket: [[utterance index] * per_rank for each rank]} = the plan with every
+    filler (-1) replaced by a real utterance the rank computes in its place (its first real one of that bucket, else the bucket's
+    first); need[r]: the distinct utterances whose records rank r needs, ascending — also the order in which exchange_records
+    delivers them (the source slices are contiguous and ascending)."""
+    slots, need = {}, [set() for _ in range(world)]
+    for b, ranks in plan.items():
+        first = min(i for r in ranks for i in r if i >= 0)
+        rows = []
+        for r, ids in enumerate(ranks):
+            real = [i for i in ids if i >= 0]
+            fill = real[0] if real else first
+            rows.append([i if i >= 0 else fill for i in ids])
+            need[r].update(rows[-1])
+        slots[b] = rows
+    return slots, [sorted(s) for s in need]
+
+
+def _pad_rows(x: torch.Tensor, n: int) -> torch.Tensor:
+    if x.shape[0] == n:
+        return x.contiguous()
+    out = torch.zeros((n,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    out[:x.shape[0]] = x
+    return out
+
+
+def allgather_lengths(mel_len: torch.Tensor, n_items: int, group=None) -> List[int]:
+    """The length agreement: every rank contributes the mel_len of its slice (shard_range) and receives all n_items, as ONE
+    all-gather of int32 (slices padded to the longest: 4 * world * ceil(n_items / world) bytes per rank)."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    if world == 1:
+        return [int(v) for v in mel_len.tolist()]
+    per = -(-n_items // world)
+    send = _pad_rows(mel_len.to(torch.int32), per)
+    out = torch.empty(world, per, dtype=torch.int32, device=send.device)
+    if dist.get_backend(group) == "gloo":
+        dist.all_gather(list(out.unbind(0)), send, group=group)
+    else:
+        dist.all_gather_into_tensor(out.reshape(-1), send, group=group)
+    flat = out.cpu().tolist()
+    res = []
+    for r in range(world):
+        lo, hi = shard_range(n_items, r, world)
+        res += flat[r][:hi - lo]
+    return res
+
+
+def exchange_records(records: torch.Tensor, need, n_items: int, group=None, force: bool = False) -> torch.Tensor:
+    """records uint8 [hi - lo, R]: this rank's slice.  Returns the records of need[rank] (route_records) in that order.
+    RCCL: ONE torch.distributed.all_to_all_single with uneven splits over the job's own process group (what a torchrun job
+    already holds; a non-Python host calls cmtts_exchange_records, the same grouped send / receive round) — each record crosses
+    the fabric once, to the rank that computes it.  gloo (CPU tests): an all-gather of the padded slices, then local selection.
+    `force` runs the collective on a 1-rank group too (single-GPU check of the call sequence)."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    lo, hi = shard_range(n_items, rank, world)
+    if world == 1 and not force:
+        return records.index_select(0, torch.tensor([i - lo for i in need[0]], dtype=torch.int64, device=records.device))
+    R = records.shape[1]
+    if dist.get_backend(group) == "gloo":
+        per = -(-n_items // world)
+        out = torch.empty(world, per, R, dtype=records.dtype, device=records.device)
+        dist.all_gather(list(out.unbind(0)), _pad_rows(records, per), group=group)
+        rows = []
+        for i in need[rank]:
+            for s in range(world):
+                slo, shi = shard_range(n_items, s, world)
+                if slo <= i < shi:
+                    rows.append(s * per + i - slo)
+        return out.reshape(world * per, R).index_select(0, torch.tensor(rows, dtype=torch.int64, device=records.device))
+    send_rows, send_split, recv_split = [], [], []
+    for p in range(world):
+        mine = [i - lo for i in need[p] if lo <= i < hi]
+        send_rows += mine
+        send_split.append(len(mine) * R)
+    for s in range(world):
+        slo, shi = shard_range(n_items, s, world)
+        recv_split.append(sum(1 for i in need[rank] if slo <= i < shi) * R)
+    send = records.index_select(0, torch.tensor(send_rows, dtype=torch.int64, device=records.device)).reshape(-1)
+    out = torch.empty(sum(recv_split), dtype=records.dtype, device=records.device)
+    dist.all_to_all_single(out, send, recv_split, send_split, group=group)
+    return out.reshape(-1, R)
+
+
+def two_phase(n_items: int, text_side, frame_side, group=None, buckets: Sequence[int] = FRAME_BUCKETS):
+    """The control flow of a sharded synthesis that starts from text, with the model steps passed in:
+      text_side(lo, hi) -> (records uint8 [hi - lo, R], mel_len int64 [hi - lo]) for this rank's slice;
+      frame_side(groups) -> [(mel [n, bucket, M], mel_len [n])], groups = [(bucket, records [n, R], utterance ids [n],
+      planned lengths [n])] for every bucket this rank computes (the ids include the fillers' stand-ins).
+    Returns {"mels": per-utterance mels [len_i, M] in the input order, "mel_len": the agreed (predicted) lengths, "planned": the
+    lengths after truncation, "truncated", "plan", "slots", "need", "records": what this rank received}."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    lo, hi = shard_range(n_items, rank, world)
+    records, mel_len = text_side(lo, hi)
+    lens = allgather_lengths(mel_len, n_items, group)
+    planned, truncated = planned_lengths(lens, buckets)
+    plan = plan_shards(planned, world, buckets)
+    slots, need = route_records(plan, n_items, world)
+    recv = exchange_records(records, need, n_items, group)
+    row = {i: k for k, i in enumerate(need[rank])}
+    groups = []
+    for b in sorted(slots):
+        ids = slots[b][rank]
+        sel = torch.tensor([row[i] for i in ids], dtype=torch.int64, device=recv.device)
+        groups.append((b, recv.index_select(0, sel), ids, [planned[i] for i in ids]))
+    outs = frame_side(groups)
+    mels = {b: outs[k] for k, (b, *_rest) in enumerate(groups)}
+    gathered = allgather_buckets(mels, group)
+    return {"mels": restore_order(gathered, plan, n_items), "mel_len": lens, "planned": planned, "truncated": truncated,
+            "plan": plan, "slots": slots, "need": need, "records": recv, "local": mels}

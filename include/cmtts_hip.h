@@ -59,9 +59,10 @@ const char* cmtts_version(void);
  * inserted cmtts_config.n_speaker and the `speakers` parameter of cmtts_text_forward: revision 2; round 3 adds entry
  * points only but starts the counter: 3; round 4 appends the conditioner factors to cmtts_sample_group: 4;
  * round 6: 5 — no layout change, but the MEANING of an existing option value changed in round 5 without a bump: cmtts_model_set_option(m, "winograd", 1) selects
- * the F(4,3) form since then and 2 the F(2,3) form that 1 used to select, and cmtts_poll_error's codes 2 / 3 no longer fail the next launch).  A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
+ * the F(4,3) form since then and 2 the F(2,3) form that 1 used to select, and cmtts_poll_error's codes 2 / 3 no longer fail the next launch);
+ * 6 — entry points only: the text-state records (cmtts_text_state_*) and cmtts_exchange_records of a sharded synthesis.  A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
  * against before it passes a struct (cmtts_amd/_lib.py does at load time). */
-#define CMTTS_ABI_VERSION 5
+#define CMTTS_ABI_VERSION 6
 int cmtts_abi_version(void);
 
 /* ---- weight import: replaces torch.load + load_state_dict (synthesize.py:79-83).
@@ -151,6 +152,27 @@ int cmtts_frame_forward_sub(cmtts_model* m, const void* text_ws, int B_all, int 
 int cmtts_frame_forward_sub_t(cmtts_model* m, const void* text_ws, int B_all, int L_all, int b0, int B, int T,
                               float* cond_ct, int64_t* mel2ph, float* cwt_out, float* f0_denorm, int64_t* p_idx,
                               float* f0_stats, float* cond_p1, float* cond_p1t, void* frame_ws, size_t frame_ws_bytes, void* stream);
+
+/* ---- text-side state of single utterances as fixed-size records (new work: the hand-off of a sharded synthesis that starts from
+ * text — each rank runs the text side of its slice of the batch, the ranks agree on the frame buckets once the lengths are known, and
+ * each utterance's state moves to the rank the plan gives it; the reference synthesizes one padded batch in one process,
+ * synthesize.py:195-227).  A record holds, for one utterance of a text workspace filled for L_all phonemes, what
+ * cmtts_frame_forward_sub reads: out1 fp32 [hidden][Lp], h128 fp32 [cwt_hidden][Lp], spk fp32 [hidden] (the speaker vector,
+ * = the speaker_emb output of the text side for multi-speaker models), cum int32 [L_all] (cumulative rounded durations: d_rounded =
+ * its differences), behind a 64-byte header { int64 global index, int64 mel_len, int32 src_len, uint32 layout = 0x54530001,
+ * int32 L_all, hidden, cwt_hidden, n_regions, 24 bytes zero }; every region starts 16-byte aligned.  The size depends on
+ * (config, L_all) only.  Records are plain bytes: any transport may move them between ranks of the same build.
+ *   pack: rows int32 [n] (device) = the workspace rows to gather, in record order; global_idx int64 [n] (device, NULL = the row) and
+ *   src_lens int64 [B_all] (device, NULL = -1) only fill the header; records [n][record_bytes] (device, 16-byte aligned).  A row
+ *   outside [0, B_all) leaves its record untouched.
+ *   unpack: scatters n records into rows 0..n-1 of a text workspace of cmtts_text_workspace_bytes(m, n, L_all) bytes;
+ *   cmtts_frame_forward_sub(_t)(m, text_ws, n, L_all, b0, B, T, ...) then runs on it unchanged and returns the bits it returns on the
+ *   workspace the records came from.
+ * Both are single bandwidth-bound launches (one 16 KB chunk of one region of one record per workgroup, 16-byte loads and stores). */
+size_t cmtts_text_state_record_bytes(const cmtts_model* m, int L_all);
+int cmtts_text_state_pack(cmtts_model* m, const void* text_ws, int B_all, int L_all, const int32_t* rows, int n, const int64_t* global_idx,
+                          const int64_t* src_lens, void* records, void* stream);
+int cmtts_text_state_unpack(cmtts_model* m, const void* records, int n, int L_all, void* text_ws, size_t text_ws_bytes, void* stream);
 
 /* ---- length regulator alone (LengthRegulator.forward, model/modules.py:446-448): bit-exact
  * gather x_ct [B,C,L] -> out_ct [B,C,T] given fp32 durations [B,L]; also emits mel2ph and mel_len.
@@ -371,6 +393,13 @@ int cmtts_allgather_mels(void* comm, int world, const float* mel, const int64_t*
 size_t cmtts_allgather_pcm_workspace_bytes(int world, int Bl, int64_t N);
 int cmtts_allgather_pcm(void* comm, int world, const int16_t* pcm, const int64_t* wav_len, int Bl, int64_t N,
                         int16_t* out_pcm, int64_t* out_len, void* ws, size_t ws_bytes, void* stream);
+
+/* Text-state records to the ranks a length plan gives them (cmtts_text_state_pack above): this rank sends send_counts[p] records
+ * to rank p and receives recv_counts[p] records from rank p, both laid out consecutively in rank order — ONE grouped round of
+ * ncclSend / ncclRecv with uneven splits, only what each rank needs (no all-gather of every record).  send_counts / recv_counts: HOST
+ * int64 [world]; record_bytes = cmtts_text_state_record_bytes.  comm NULL (world 1): the records are copied.  Enqueued on `stream`. */
+int cmtts_exchange_records(void* comm, int world, const void* send, const int64_t* send_counts, void* recv, const int64_t* recv_counts,
+                           size_t record_bytes, void* stream);
 
 /* ---- get_mask_from_lengths (utils/tools.py:275-283): mask[b][t] = (t >= lens[b]) as one byte per element
  * (True = padding), lens int64 [B], mask [B,W]. */
