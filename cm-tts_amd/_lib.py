@@ -73,6 +73,9 @@ SIGNATURES = {
     "cmtts_vocoder_workspace_bytes": (_sz, [_vp, _i, _i]),
     "cmtts_vocoder_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "cmtts_wav_to_int16": (_i, [_vp, _vp, _i64, _f, _vp]),
+    "cmtts_vocoder_halo_frames": (_i, [_vp]),
+    "cmtts_vocoder_windows_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "cmtts_vocoder_forward_windows": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _f, _vp, _sz, _vp]),
     "cmtts_profile_begin": (_i, [_i, _i]),
     "cmtts_set_fused_resblock": (_i, [_i]),
     "cmtts_set_persistent_denoiser": (_i, [_i]),
@@ -102,7 +105,7 @@ SIGNATURES = {
     "cmtts_conv1d": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
-ABI_VERSION = 6          # include/cmtts_hip.h: CMTTS_ABI_VERSION
+ABI_VERSION = 7          # include/cmtts_hip.h: CMTTS_ABI_VERSION
 _lib = None
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cmtts_hip.h")
 

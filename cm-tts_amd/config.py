@@ -76,6 +76,24 @@ class HifiGanConfig:
             h *= u
         return h
 
+    @property
+    def halo_frames(self) -> int:
+        """Receptive radius of the generator in mel frames: output frame f depends on mel frames [f - H, f + H] only.
+        Propagates the interval of output samples of one frame backwards through conv_post, every MRF (the widest
+        ResBlock: each (conv1 dilation d, conv2) pair widens by (d + 1) (k - 1) / 2), the ConvTranspose1d upsamplers and
+        conv_pre (the same walk as cmtts_vocoder_halo_frames).  13 for V1."""
+        f = 1 << 20                              # a frame far from both ends: no clamping
+        lo, hi = f * self.hop, (f + 1) * self.hop - 1
+        lo, hi = lo - 3, hi + 3                  # conv_post k = 7
+        for u, k in reversed(tuple(zip(self.upsample_rates, self.upsample_kernel_sizes))):
+            w = max(sum((d + 1) * (rk - 1) // 2 for d in dils)
+                    for rk, dils in zip(self.resblock_kernel_sizes, self.resblock_dilation_sizes))
+            lo, hi = lo - w, hi + w
+            p = (k - u) // 2                     # y[t] = sum over i u + j - p = t of x[i] w[j], j in [0, k)
+            lo, hi = -((-(lo + p - (k - 1))) // u), (hi + p) // u
+        lo, hi = lo - 3, hi + 3                  # conv_pre k = 7
+        return max(f - lo, hi - f)
+
 
 VARIANTS = {
     "LJSpeech": CMTTSConfig(name="LJSpeech", multi_speaker=False, use_uv=True),

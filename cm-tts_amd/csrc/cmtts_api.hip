@@ -24,6 +24,7 @@
 #include "inproj.h"
 #include "attention.h"
 #include "text_state.h"
+#include "stream_windows.h"
 
 namespace {
 
@@ -2620,12 +2621,11 @@ size_t cmtts_vocoder_workspace_bytes(const cmtts_vocoder* v, int B, int T) {
     const int nb = (long)B * T <= VOC_PAR_FRAMES ? 9 : 5;
     return (size_t)nb * (((size_t)B * T * 8192 + (size_t)B * 512 * voc_row_pad()) * sizeof(float) + 256) + 256;
 }
-int cmtts_vocoder_forward(cmtts_vocoder* v, const float* mel_ct, int B, int T, float* wav, void* ws, size_t ws_bytes,
-                          void* stream) {
-    if (!v || !v->finalized) return fail(CMTTS_E_INVALID, "vocoder not finalized");
-    if (!mel_ct || !wav || !ws || B <= 0 || T <= 0) return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward: bad argument");
-    if (ws_bytes < cmtts_vocoder_workspace_bytes(v, B, T)) return fail(CMTTS_E_WORKSPACE, "vocoder workspace too small");
-    hipStream_t s = (hipStream_t)stream;
+// The generator up to (not including) its last layer: mel_ct [B,80,T] -> the last MRF sum [B][ch][ld] with Ti = 256 T valid columns
+// (*x_out, still to be divided by the ResBlock count; ld = Ti + row pad), in the workspace of cmtts_vocoder_workspace_bytes(v, B, T).
+// Shared by cmtts_vocoder_forward (whole mels) and cmtts_vocoder_forward_windows (a batch of mel windows).
+static int vocoder_generator(cmtts_vocoder* v, const float* mel_ct, int B, int T, void* ws, hipStream_t s, const float** x_out,
+                             int* ch_out, int* Ti_out, int* ld_out) {
     Carver cv(ws);
     const int P = voc_row_pad();
     const size_t nbuf = (size_t)B * T * 8192 + (size_t)B * 512 * P;
@@ -2888,10 +2888,115 @@ int cmtts_vocoder_forward(cmtts_vocoder* v, const float* mel_ct, int B, int T, f
         float* t = bufA; bufA = bufS; bufS = t;
         Ti = To; ch = co;
     }
+    *x_out = bufA; *ch_out = ch; *Ti_out = Ti; *ld_out = Ti + P;
+    return 0;
+}
+int cmtts_vocoder_forward(cmtts_vocoder* v, const float* mel_ct, int B, int T, float* wav, void* ws, size_t ws_bytes,
+                          void* stream) {
+    if (!v || !v->finalized) return fail(CMTTS_E_INVALID, "vocoder not finalized");
+    if (!mel_ct || !wav || !ws || B <= 0 || T <= 0) return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward: bad argument");
+    if (ws_bytes < cmtts_vocoder_workspace_bytes(v, B, T)) return fail(CMTTS_E_WORKSPACE, "vocoder workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const float* x = nullptr;
+    int ch = 0, Ti = 0, ld = 0;
+    if (const int rc = vocoder_generator(v, mel_ct, B, T, ws, s, &x, &ch, &Ti, &ld)) return rc;
     // x = leaky_relu(xs / 3) [slope 0.01] -> conv_post -> tanh (:161-163)
-    k_conv_post(bufA, v->post_w, v->post_b, 3.0f, 0.01f, wav, B, ch, Ti, Ti + P, v->post_k, s);
+    k_conv_post(x, v->post_w, v->post_b, 3.0f, 0.01f, wav, B, ch, Ti, ld, v->post_k, s);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// ---- streaming: a batch of mel windows through the generator, int16 chunks of the window cores out (stream_windows.hip)
+int cmtts_vocoder_halo_frames(const cmtts_vocoder* v) {
+    // output frame f depends on mel frames [f - H, f + H]: the samples of frame f propagated backwards through conv_post,
+    // every MRF (widest ResBlock: a (conv1 dilation d, conv2) pair widens by (d + 1)(k - 1) / 2), every ConvTranspose1d and
+    // conv_pre (config.HifiGanConfig.halo_frames walks the same chain)
+    if (!v) return fail(CMTTS_E_INVALID, "cmtts_vocoder_halo_frames: null argument");
+    long hop = 1;
+    for (int i = 0; i < 4; ++i) hop *= v->up_rate[i];
+    const long f = 1L << 20;
+    long lo = f * hop - v->post_k / 2, hi = (f + 1) * hop - 1 + v->post_k / 2;
+    int w = 0;
+    for (int j = 0; j < 3; ++j) w = std::max(w, (v->rb_dil[0] + v->rb_dil[1] + v->rb_dil[2] + 3) * (v->rb_kernel[j] - 1) / 2);
+    for (int i = 3; i >= 0; --i) {
+        const long u = v->up_rate[i], k = v->up_kernel[i], p = (k - u) / 2;
+        lo -= w; hi += w;
+        const long a = lo + p - (k - 1), b = hi + p;          // y[t] = sum over i u + j - p = t (j in [0, k)) of x[i] w[j]
+        lo = a >= 0 ? (a + u - 1) / u : -((-a) / u);
+        hi = b >= 0 ? b / u : -((-b + u - 1) / u);
+    }
+    lo -= 3; hi += 3;                                          // conv_pre k = 7
+    return (int)std::max(f - lo, hi - f);
+}
+size_t cmtts_vocoder_windows_workspace_bytes(const cmtts_vocoder* v, int N, int Tw) {
+    if (N <= 0 || Tw <= 0) return 0;
+    // the gathered windows [N][80][Tw] and the validated table [N][4], then the generator's workspace for (N, Tw)
+    return (((size_t)N * 80 * Tw * sizeof(float) + 255) & ~(size_t)255) + (((size_t)N * sizeof(StreamWindow) + 255) & ~(size_t)255) +
+           cmtts_vocoder_workspace_bytes(v, N, Tw);
+}
+int cmtts_vocoder_forward_windows(cmtts_vocoder* v, const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, int core,
+                                  int16_t* pcm, float max_wav_value, void* ws, size_t ws_bytes, void* stream) {
+    if (!v || !v->finalized) return fail(CMTTS_E_INVALID, "vocoder not finalized");
+    if (!mel_ct || !windows || !pcm || !ws) return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward_windows: null argument");
+    if (B <= 0 || T <= 0 || N <= 0 || Tw <= 0 || core <= 0)
+        return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward_windows: B, T, N, Tw and core must be positive");
+    if (Tw > T) return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward_windows: Tw > T");
+    if (!(max_wav_value > 0.f && max_wav_value <= 32768.f)) return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward_windows: max_wav_value outside (0, 32768]");
+    if (ws_bytes < cmtts_vocoder_windows_workspace_bytes(v, N, Tw)) return fail(CMTTS_E_WORKSPACE, "cmtts_vocoder_forward_windows: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    // The table is validated on the host before anything launches: a page-locked host table is read in place and copied into the
+    // workspace on `stream` (no synchronisation; the caller keeps it unchanged until the call's work has completed); a device table is
+    // read back first, which synchronises `stream`.
+    std::vector<StreamWindow> tab(N);
+    hipPointerAttribute_t at{};
+    const bool known = hipPointerGetAttributes(&at, windows) == hipSuccess;
+    if (!known) (void)hipGetLastError();
+    const bool on_host = known && at.type == hipMemoryTypeHost;
+    const bool on_dev = known && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeUnified);
+    if (!on_host && !on_dev) return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward_windows: the window table must be device or page-locked host memory");
+    if (on_host) {
+        memcpy(tab.data(), windows, (size_t)N * sizeof(StreamWindow));
+    } else {
+        HIPCHK(hipMemcpyAsync(tab.data(), windows, (size_t)N * sizeof(StreamWindow), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    for (int n = 0; n < N; ++n) {
+        const StreamWindow& w = tab[n];
+        char msg[200];
+        const char* bad = w.b < 0 || w.b >= B                                   ? "utterance outside [0, B)"
+                          : w.start < 0 || (long)w.start + Tw > T              ? "window outside [0, T)"
+                          : w.core_len <= 0 || w.core_len > core               ? "core_len outside [1, core]"
+                          : w.core_off < 0 || (long)w.core_off + w.core_len > Tw ? "core_off + core_len > Tw"
+                                                                                  : nullptr;
+        if (bad) {
+            snprintf(msg, sizeof msg, "cmtts_vocoder_forward_windows: window %d (%d, %d, %d, %d): %s", n, w.b, w.start, w.core_off, w.core_len, bad);
+            return fail(CMTTS_E_INVALID, msg);
+        }
+    }
+    Carver cv(ws);
+    float* mel_w = cv.take<float>((size_t)N * 80 * Tw);
+    StreamWindow* win = cv.take<StreamWindow>(N);
+    void* gws = cv.base + ((cv.off + 255) & ~(size_t)255);
+    if (on_host) HIPCHK(hipMemcpyAsync(win, windows, (size_t)N * sizeof(StreamWindow), hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpyAsync(win, windows, (size_t)N * sizeof(StreamWindow), hipMemcpyDeviceToDevice, s));
+    if (cmtts_launch_mel_window_gather(mel_ct, 80, T, win, N, Tw, mel_w, (void*)s) != 0) return fail(CMTTS_E_HIP, "mel window gather launch failed");
+    const float* x = nullptr;
+    int ch = 0, Ti = 0, ld = 0;
+    if (const int rc = vocoder_generator(v, mel_w, N, Tw, gws, s, &x, &ch, &Ti, &ld)) return rc;
+    long hop = 1;
+    for (int i = 0; i < 4; ++i) hop *= v->up_rate[i];
+    // x = leaky_relu(xs / 3) [slope 0.01] -> conv_post -> tanh -> int16, core columns only
+    const int rc = cmtts_launch_conv_post_windows(x, v->post_w, v->post_b, 3.0f, 0.01f, win, N, ch, Ti, ld, v->post_k, (int)hop, core,
+                                                  max_wav_value, pcm, (void*)s);
+    if (rc == -2) return fail(CMTTS_E_UNSUPPORTED, "cmtts_vocoder_forward_windows: conv_post kernel wider than 7");
+    if (rc != 0) return fail(CMTTS_E_HIP, "conv_post windows launch failed");
+    return 0;
+}
+int cmtts_internal_mel_window_gather(const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, float* out, void* stream) {
+    (void)B;
+    if (!mel_ct || !windows || !out || N <= 0 || Tw <= 0 || Tw > T) return fail(CMTTS_E_INVALID, "cmtts_internal_mel_window_gather: bad argument");
+    return cmtts_launch_mel_window_gather(mel_ct, 80, T, (const StreamWindow*)windows, N, Tw, out, stream) == 0 ? 0
+                                                                                                              : fail(CMTTS_E_HIP, "gather launch failed");
 }
 
 // ---- options.  Three tiers:

@@ -31,6 +31,9 @@ int cmtts_internal_cond_projections(struct cmtts_model* m, const float* cond_ct,
 // Test hook: the same tensor expanded from the factors cmtts_frame_forward_sub returns (cond_p1 [B][NL*C][p1_ld], mel2ph, p_idx [B][T])
 int cmtts_internal_cond_factored(struct cmtts_model* m, const float* p1, int p1_ld, int L, const int64_t* mel2ph, const int64_t* p_idx, int B, int T,
                                  float* cp, void* stream);
+// Test hook: the streaming rounds' mel window gather alone (stream_windows.hip: mel_window_gather_kernel).  mel_ct [B][80][T] ->
+// out [N][80][Tw], windows: device [N][4] int32 (utterance, start, core_off, core_len) — NOT validated here (the caller's test does).
+int cmtts_internal_mel_window_gather(const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, float* out, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -786,7 +786,7 @@ class Generator(torch.nn.Module):
     def eval(self):
         return self
 
-    def forward(self, x):
+    def _require(self):
         if not self._ready and getattr(self, "_pending", False):
             if not torch.cuda.is_available():
                 raise RuntimeError("Generator: no GPU — cmtts_amd has no CPU fallback (the weights are loaded, the kernels cannot run)")
@@ -794,6 +794,9 @@ class Generator(torch.nn.Module):
             self._finalize()
         if not self._ready:
             raise RuntimeError("Generator: load_state_dict() first")
+
+    def forward(self, x):
+        self._require()
         dev = self.device
         x = _f32(x, dev)
         B, M, T = x.shape
@@ -825,6 +828,149 @@ def vocoder_infer(mels, vocoder, model_config=None, preprocess_config=None, leng
     if lengths is not None:
         out = [w[: int(lengths[i])] for i, w in enumerate(out)]
     return out
+
+
+# ----------------------------------------------------------------------------- streamed PCM (DESIGN.md §3 "Streaming")
+
+STREAM_CHUNK_FRAMES = (32, 64, 128, 256)
+
+
+def vocoder_halo_frames(hcfg: HifiGanConfig = None):
+    """Receptive radius of the generator in mel frames (config.HifiGanConfig.halo_frames; 13 for V1)."""
+    return (hcfg if hcfg is not None else HifiGanConfig()).halo_frames
+
+
+class StreamRound:
+    """One round of a stream plan: every window Tw mel frames wide, chunk rows of `core` frames, windows = [(utterance, window
+    start, core offset in the window, core length)] — the int32 [N][4] table of cmtts_vocoder_forward_windows."""
+    __slots__ = ("Tw", "core", "windows")
+
+    def __init__(self, Tw, core, windows):
+        self.Tw, self.core, self.windows = Tw, core, windows
+
+    def __repr__(self):
+        return f"StreamRound(Tw={self.Tw}, core={self.core}, windows={self.windows})"
+
+
+def plan_stream_windows(T, mel_lens, chunk_frames=STREAM_CHUNK_FRAMES, halo=13):
+    """Windows of a streamed vocoding of a padded mel [B, 80, T] whose utterances hold mel_lens[b] frames.  Round r vocodes the next
+    chunk_frames[r] frames (the last entry repeats; at most the longest remainder) of every utterance not finished yet, in windows Tw = core + 2 halo wide that all lie
+    inside [0, T): a window starts `halo` frames before its core unless that would cross 0 or T, where it shifts inwards (the whole-mel
+    run sees zero padding at every layer only at the tensor's ends; zero mel frames are not the same, conv_pre's bias makes them non-zero)
+    and its core offset grows.  When core + 2 halo >= T the round is one whole-tensor window per utterance (Tw = core = T) holding
+    everything left.  Cores tile [0, mel_lens[b]) exactly; an utterance's last core may be short.  Zero-length utterances get no window.
+    Returns [StreamRound]."""
+    T, halo = int(T), int(halo)
+    lens = [int(n) for n in mel_lens]
+    chunks = [int(c) for c in chunk_frames]
+    if T <= 0 or halo < 0 or not chunks or min(chunks) <= 0:
+        raise ValueError(f"plan_stream_windows: T = {T}, halo = {halo}, chunk_frames = {chunks}")
+    if any(n < 0 or n > T for n in lens):
+        raise ValueError(f"plan_stream_windows: mel_lens {lens} outside [0, {T}]")
+    pos = [0] * len(lens)
+    live = [b for b, n in enumerate(lens) if n > 0]
+    rounds = []
+    while live:
+        # no wider than the longest remainder: a final round of short cores does not pay for a full-width window
+        c = min(chunks[min(len(rounds), len(chunks) - 1)], max(lens[b] - pos[b] for b in live))
+        wins = []
+        if c + 2 * halo >= T:
+            Tw = core = T
+            for b in live:
+                wins.append((b, 0, pos[b], lens[b] - pos[b]))
+        else:
+            Tw, core = c + 2 * halo, c
+            for b in live:
+                cs = pos[b]
+                start = min(max(cs - halo, 0), T - Tw)
+                wins.append((b, start, cs - start, min(c, lens[b] - cs)))
+        for b, start, off, n in wins:
+            pos[b] = start + off + n
+        rounds.append(StreamRound(Tw, core, wins))
+        live = [b for b in live if pos[b] < lens[b]]
+    return rounds
+
+
+def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_FRAMES, max_wav_value=32768.0):
+    """vocoder_infer, streamed: mels [B,80,T] -> a generator of (utterance, sample_offset, pcm int16 numpy, is_last), round by round
+    (plan_stream_windows; lengths = mel FRAMES per utterance, default T — vocoder_infer's `lengths` count samples).  Concatenated per
+    utterance the chunks are vocoder_infer(mels, lengths=mel_len * hop)'s output: bitwise with the direct fp32 form ("winograd" 0),
+    within the conv forms' rounding otherwise.  Round r + 1 is enqueued on the current stream before round r's chunks are
+    handed back; each round's int16 rows go to pinned host memory on a copy stream, so that copy overlaps the next round's generator."""
+    vocoder._require()
+    lib, dev = vocoder.lib, vocoder.device
+    x = _f32(mels, dev)
+    B, M, T = x.shape
+    lens = [T] * B if lengths is None else [int(n) for n in lengths]
+    if len(lens) != B:
+        raise ValueError(f"vocoder_infer_stream: {len(lens)} lengths for {B} mels")
+    halo = lib.cmtts_vocoder_halo_frames(vocoder._h)
+    if halo < 0:
+        _lib.check(halo)
+    hop = vocoder.h.hop
+    rounds = plan_stream_windows(T, lens, chunk_frames, halo)
+    if not rounds:
+        return
+    with torch.cuda.device(dev):
+        comp = torch.cuda.current_stream(dev)
+        copy = torch.cuda.Stream(dev)
+        nb = max(lib.cmtts_vocoder_windows_workspace_bytes(vocoder._h, len(r.windows), r.Tw) for r in rounds)
+        ws = vocoder._ws.get("voc_stream", nb, dev)
+
+        def enqueue(r):
+            N = len(r.windows)
+            tab = torch.tensor(r.windows, dtype=torch.int32).pin_memory()      # read in place by the call: kept until `done`
+            pcm = torch.empty(N, r.core * hop, dtype=torch.int16, device=dev)
+            _lib.check(lib.cmtts_vocoder_forward_windows(vocoder._h, _ptr(x), B, T, _ptr(tab), N, r.Tw, r.core, _ptr(pcm),
+                                                         float(max_wav_value), _ptr(ws), nb, _stream()))
+            ready = torch.cuda.Event()
+            ready.record(comp)
+            host = torch.empty(N, r.core * hop, dtype=torch.int16, pin_memory=True)
+            with torch.cuda.stream(copy):
+                copy.wait_event(ready)
+                host.copy_(pcm, non_blocking=True)
+                pcm.record_stream(copy)
+                done = torch.cuda.Event()
+                done.record(copy)
+            return r, tab, host, done
+
+        pending = [enqueue(rounds[0])]
+        try:
+            for i in range(len(rounds)):
+                if i + 1 < len(rounds):
+                    pending.append(enqueue(rounds[i + 1]))
+                r, _tab, host, done = pending[0]
+                done.synchronize()
+                check_async_error()          # the round's launches completed: a failure reported by them is raised here
+                pending.pop(0)
+                arr = host.numpy()
+                for n, (b, start, off, cl) in enumerate(r.windows):
+                    f0 = start + off
+                    yield b, f0 * hop, arr[n, : cl * hop].copy(), f0 + cl >= lens[b]
+        finally:
+            # a consumer that stops early: the pinned tables of rounds still in flight are read by their calls' copies
+            for p in pending:
+                p[3].synchronize()
+
+
+def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=None, speakers=None, n_steps=4, noise=None,
+                      chunk_frames=STREAM_CHUNK_FRAMES, generator=None, max_wav_value=32768.0):
+    """Text -> streamed PCM: the duration net and the T-step sampler exactly as CMTotalTTSSynthesize.synthesize runs them (noise
+    [n_noise, B, 1, T, 80] drawn as x0 = randn, then randn_like(x0) per further step, unless given), then vocoder_infer_stream on
+    the mels trimmed to their predicted lengths.  Yields (utterance, sample_offset, pcm int16 numpy, is_last)."""
+    out = model.duration_pitch_energy_net(speakers=speakers, texts=texts, src_lens=src_lens, spker_embeds=spker_embeds)
+    B, T, _ = out["cond"].shape
+    cfg = model.config
+    if n_steps not in (1, 2, 4):
+        raise ValueError("n_steps must be 1, 2 or 4 (synthesize.py:111-147)")
+    draws = 1 if n_steps == 1 else n_steps + 1
+    if noise is None:
+        gen = generator or DummyGenerator()
+        x0 = gen.randn(B, 1, T, cfg.n_mels, device=model.device)
+        noise = torch.stack([x0] + [gen.randn_like(x0) for _ in range(draws - 1)], 0).float()
+    mel = sample_with_cond(model, out["cond_ct"], out["speaker_emb"], n_steps, noise, factors=out.get("cond_factors"))
+    mel_lens = out["mel_lens"].cpu().tolist()
+    yield from vocoder_infer_stream(mel.transpose(1, 2), vocoder, mel_lens, chunk_frames, max_wav_value)
 
 
 def synth_samples(args, targets, predictions, vocoder, model_config, preprocess_config, path, diffusion=None):

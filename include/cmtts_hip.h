@@ -60,9 +60,11 @@ const char* cmtts_version(void);
  * points only but starts the counter: 3; round 4 appends the conditioner factors to cmtts_sample_group: 4;
  * round 6: 5 — no layout change, but the MEANING of an existing option value changed in round 5 without a bump: cmtts_model_set_option(m, "winograd", 1) selects
  * the F(4,3) form since then and 2 the F(2,3) form that 1 used to select, and cmtts_poll_error's codes 2 / 3 no longer fail the next launch);
- * 6 — entry points only: the text-state records (cmtts_text_state_*) and cmtts_exchange_records of a sharded synthesis.  A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
+ * 6 — entry points only: the text-state records (cmtts_text_state_*) and cmtts_exchange_records of a sharded synthesis;
+ * 7 — entry points only: windowed vocoding for streamed PCM (cmtts_vocoder_halo_frames, cmtts_vocoder_windows_workspace_bytes,
+ * cmtts_vocoder_forward_windows).  A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
  * against before it passes a struct (cmtts_amd/_lib.py does at load time). */
-#define CMTTS_ABI_VERSION 6
+#define CMTTS_ABI_VERSION 7
 int cmtts_abi_version(void);
 
 /* ---- weight import: replaces torch.load + load_state_dict (synthesize.py:79-83).
@@ -260,6 +262,26 @@ int cmtts_vocoder_forward(cmtts_vocoder* v, const float* mel_ct, int B, int T, f
                           void* ws, size_t ws_bytes, void* stream);
 /* vocoder_infer's cast (utils/model.py:195-198): pcm = (wav * max_wav_value).astype(int16) */
 int cmtts_wav_to_int16(const float* wav, int16_t* pcm, int64_t n, float max_wav_value, void* stream);
+
+/* ---- streamed PCM: windowed vocoding (DESIGN.md §3 "Streaming").  The generator is purely convolutional: output
+ * frame f (samples [256 f, 256 f + 256)) depends on mel frames [f - H, f + H] only, H = cmtts_vocoder_halo_frames(v) (13 for V1).
+ * So a mel can be vocoded in windows whose CORES tile each utterance, every window reaching at least H frames beyond its core
+ * unless it is clamped at 0 or T (the only places where the whole-mel run sees zero padding): the core samples are those of
+ * cmtts_vocoder_forward + cmtts_wav_to_int16 on the whole mel — bitwise in the direct fp32 form ("winograd" 0), within the
+ * forms' rounding otherwise (the window batch may take another conv form than the whole batch).
+ * cmtts_vocoder_forward_windows: mel_ct fp32 [B,80,T] (device); windows int32 [N][4] = (utterance b, window start, core_off, core_len):
+ * window n is mel frames [start, start + Tw) of utterance b (0 <= start, start + Tw <= T), its core frames
+ * [start + core_off, start + core_off + core_len) with 1 <= core_len <= core and core_off + core_len <= Tw.  pcm int16 [N, core * 256]
+ * (device): row n holds the core's int16 samples, (int16)(int)(tanh(.) * max_wav_value) exactly as cmtts_wav_to_int16, then zeros
+ * after a short core.  Only the generator's last layer (conv_post + tanh + the cast) is restricted to the core columns.
+ * The table may be device memory or page-locked host memory; it is VALIDATED on the host before anything is launched (a bad
+ * argument or window returns CMTTS_E_INVALID and launches nothing; a short workspace CMTTS_E_WORKSPACE).  A device table is
+ * read back first, which synchronises `stream`; a page-locked host table is read in place and copied on `stream`, so the
+ * caller keeps it unchanged until the call's work has completed.  ws: cmtts_vocoder_windows_workspace_bytes(v, N, Tw) bytes. */
+int cmtts_vocoder_halo_frames(const cmtts_vocoder* v);
+size_t cmtts_vocoder_windows_workspace_bytes(const cmtts_vocoder* v, int N, int Tw);
+int cmtts_vocoder_forward_windows(cmtts_vocoder* v, const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, int core,
+                                  int16_t* pcm, float max_wav_value, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- measurement hook (no reference counterpart; the reference's only perf tooling is the
  * wall-clock Timer of p_rtf_cm.py:64-108): HIP events recorded on the launch stream around every
