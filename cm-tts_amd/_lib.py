@@ -105,7 +105,7 @@ SIGNATURES = {
     "cmtts_conv1d": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
-ABI_VERSION = 7          # include/cmtts_hip.h: CMTTS_ABI_VERSION
+ABI_VERSION = 8         # include/cmtts_hip.h: CMTTS_ABI_VERSION
 _lib = None
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cmtts_hip.h")
 

@@ -705,6 +705,7 @@ struct cmtts_model {
     int text16 = 0;        // 16-bit models (precision 1 / 2): the FFN contractions of the FFT blocks with 16-bit operands too (opt-in: the text side feeds the integer stages — durations, pitch buckets, lengths — which then depend on the precision mode; cmtts_model_set_option)
     int winograd = 1;                       // fp32 persistent denoiser: Winograd k = 3 conv (cmtts_model_set_option "winograd"): 1 = F(4,3) (~8e-6 on the mel against the direct form),
                                             // 2 = F(2,3) (~4e-6), 0 = direct
+    int batch_invariant = 0;                // fp32, winograd = 1: the per-layer residual blocks in the persistent stack's F(4,3) form (cmtts_model_set_option "batch_invariant")
     int ffn2_split = 1;    // FFT blocks: the FFN linear as 8 partial GEMMs over K segments + one reduction (another fp32 summation order than one launch: a property of the model handle, cmtts_model_set_option)
     cmtts_variance_controls vc = {1.f, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     Allocs al;
@@ -760,7 +761,8 @@ struct cmtts_vocoder {
     float *c1q32[12][3] = {}, *c2q32[12][3] = {};    // F(4,3) fragments of the dilation-1 convs (conv_xlq_kernel; c1q32 only for the first pair of a ResBlock), else null
     float *c1w32[12][3] = {}, *c2w32[12][3] = {};    // Winograd-transformed fragments of the C >= 128 stages (conv_xlw_kernel), else null
     int winograd = 1;                                 // fp32 generator: ResBlock convs of the C >= 128 stages in their Winograd form (cmtts_vocoder_set_option "winograd")
-    int precision = 0;                                // 0 fp32, 1 bf16, 2 fp16 operands in the ResBlock convs
+    int batch_invariant = 0;                          // fp32 generator: every launch-size gate takes its large-launch branch (cmtts_vocoder_set_option "batch_invariant")
+    int precision = 0;                               // 0 fp32, 1 bf16, 2 fp16 operands in the ResBlock convs
     int ups16 = 1;                                    // 16-bit modes: upsampler operands in 16 bits as well (cmtts_vocoder_set_option "ups16"; 0 = fp32 upsamplers, different numerics)
     float *post_w = nullptr, *post_b = nullptr;
     int post_cin = 32, post_k = 7;
@@ -1492,6 +1494,20 @@ int denoiser_prologue(cmtts_model* m, const DenWs& w, const float* x_src, float 
     return 0;
 }
 
+// Model option "batch_invariant" (fp32 models): 1 = the per-layer residual blocks take the persistent stack's F(4,3) form
+// (resblock_split_w43.hip), so that an utterance's bits do not depend on whether its batch took that stack; 0 = off or nothing to do (the
+// stack runs the direct form, or a 16-bit model: one form at every shape); -1 = the stack would run F(2,3), which has no per-layer
+// counterpart: every denoiser call refuses before it launches anything.
+int batch_invariant_form(const cmtts_model* m) {
+    if (!m->batch_invariant || m->precision != 0 || !m->winograd || !g_persist_wino || !m->res[0].w3w) return 0;
+    return m->winograd == 1 && g_persist_wino == 3 && m->res[0].w3w43 ? 1 : -1;
+}
+int check_batch_invariant(const cmtts_model* m) {
+    if (batch_invariant_form(m) >= 0) return 0;
+    return fail(CMTTS_E_UNSUPPORTED, "batch_invariant: the persistent denoiser stack runs the F(2,3) form (model option \"winograd\" = 2), "
+                                     "which has no per-layer counterpart; set \"winograd\" to 1 or 0");
+}
+
 int denoiser_core(cmtts_model* m, const DenWs& w, const float* x_src, float in_scale, const float* timesteps,
                   const float* cond_ct, const float* spk, int B, int T, const MelPost& post, hipStream_t s, bool embed = true,
                   SideStream* pending = nullptr, float t_host = NAN,    // pending: a side branch (the conditioner GEMM) to join before the layers
@@ -1558,6 +1574,8 @@ int denoiser_core(cmtts_model* m, const DenWs& w, const float* x_src, float in_s
         CHK(cond_factored(m, w, *cfk, B, T, s));
         if (cp_ready) *cp_ready = true;
     }
+    // "batch_invariant": every layer below takes the persistent stack's F(4,3) form (the fused, split and three-launch routes alike)
+    const bool w43 = batch_invariant_form(m) > 0;
     for (int l = 0; l < NL && !layers_done; ++l) {
         const ResLayer& R = m->res[l];
         const bool prof = g_prof.on && g_prof.used + 2 <= g_prof.ev.size() && (g_prof.seen++ % g_prof.stride) == 0;
@@ -1576,7 +1594,10 @@ int denoiser_core(cmtts_model* m, const DenWs& w, const float* x_src, float in_s
                 // workgroups per tile in two launches finish sooner (measured crossover, tools/latency_bench.py)
                 const long tiles32 = (long)((T + 31) / 32) * B;
                 ra.z = w.zb;
-                if (g_split_resblock == 2 || (g_split_resblock == 1 && tiles32 <= SPLIT_MAX_TILES)) lrc = cmtts_launch_resblock_split(&ra, (void*)s);
+                if (w43) {
+                    ra.W3f = R.w3w43;
+                    lrc = cmtts_launch_resblock_w43(&ra, (void*)s);
+                } else if (g_split_resblock == 2 || (g_split_resblock == 1 && tiles32 <= SPLIT_MAX_TILES)) lrc = cmtts_launch_resblock_split(&ra, (void*)s);
                 else lrc = cmtts_launch_resblock(&ra, (void*)s);
             } else {
                 ra.W3f = (const float*)R.w3f16[m->precision - 1];
@@ -1593,6 +1614,17 @@ int denoiser_core(cmtts_model* m, const DenWs& w, const float* x_src, float in_s
             a.out[0].bvec = dp + (long)l * C; a.out[0].bvec_zs = (long)NL * C;
             a.out[0].res = hcur; a.out[0].r_zs0 = cs; a.out[0].ldr = T;
             CHK(launch(a, EPI_PLAIN, B, s));
+        }
+        if (w43) {   // "batch_invariant": the F(4,3) conv on that u, then the split projection kernel; x ping-pongs (u is consumed first)
+            ResArgs ra;
+            memset(&ra, 0, sizeof(ra));
+            ra.u = halt; ra.x_in = hcur; ra.x_out = halt; ra.skip = w.skip; ra.z = w.zb;
+            ra.d = w.dproj + (long)l * C; ra.dp = dp + (long)l * C; ra.cp = w.cp;
+            ra.W3f = R.w3w43; ra.b3 = R.b3f; ra.Wof = R.wof; ra.bo = R.outp.bias;
+            ra.vec_stride = (long)NL * C; ra.B = B; ra.T = T; ra.accum_skip = l > 0;
+            if (cmtts_launch_resblock_w43(&ra, (void*)s) != 0) return fail(CMTTS_E_HIP, "F(4,3) residual block launch failed");
+            float* t = hcur; hcur = halt; halt = t;
+            continue;
         }
         {   // z = sigmoid(gate) * tanh(filter) of the k=3 conv        (:675-679)
             ConvArgs a = conv_args(R.conv3, halt, T, T, cs, w.zb, T, cs, T);
@@ -2150,6 +2182,7 @@ int cmtts_denoiser_forward(cmtts_model* m, const float* x, const float* timestep
     if (!m || !m->finalized) return fail(CMTTS_E_INVALID, "model not finalized");
     if (!x || !timesteps || !cond_ct || !out || !ws || B <= 0 || T <= 0)
         return fail(CMTTS_E_INVALID, "cmtts_denoiser_forward: bad argument");
+    CHK(check_batch_invariant(m));
     DenWs w = carve_den(m->cfg, B, T, ws);
     if (ws_bytes < w.bytes) return fail(CMTTS_E_WORKSPACE, "denoiser workspace too small");
     hipStream_t s = (hipStream_t)stream;
@@ -2263,6 +2296,7 @@ int cmtts_sample(cmtts_model* m, const float* noise, const float* cond_ct, const
     if (!m || !m->finalized) return fail(CMTTS_E_INVALID, "model not finalized");
     if (!noise || !cond_ct || !mel || !ws || !sigmas || !renoise_std || B <= 0 || T <= 0 || n_steps < 1)
         return fail(CMTTS_E_INVALID, "cmtts_sample: bad argument");
+    CHK(check_batch_invariant(m));
     const cmtts_config& c = m->cfg;
     DenWs w = carve_den(c, B, T, ws);
     if (ws_bytes < w.bytes) return fail(CMTTS_E_WORKSPACE, "denoiser workspace too small");
@@ -2286,6 +2320,7 @@ int cmtts_sample_factored_t(cmtts_model* m, const float* noise, const float* con
     if (!noise || !cond_ct || !mel || !ws || !sigmas || !renoise_std || B <= 0 || T <= 0 || n_steps < 1)
         return fail(CMTTS_E_INVALID, "cmtts_sample_factored: bad argument");
     if (cond_p1 && (!mel2ph || !p_idx || L <= 0 || p1_ld < L)) return fail(CMTTS_E_INVALID, "cmtts_sample_factored: incomplete factors");
+    CHK(check_batch_invariant(m));
     const cmtts_config& c = m->cfg;
     DenWs w = carve_den(c, B, T, ws);
     if (ws_bytes < w.bytes) return fail(CMTTS_E_WORKSPACE, "denoiser workspace too small");
@@ -2305,6 +2340,7 @@ int cmtts_sample_ragged(cmtts_model* m, const cmtts_sample_group* groups, int n_
     if (!m || !m->finalized) return fail(CMTTS_E_INVALID, "model not finalized");
     if (!groups || n_groups < 1 || n_steps < 1 || !sigmas || !renoise_std || tail_frames < 0)
         return fail(CMTTS_E_INVALID, "cmtts_sample_ragged: bad argument");
+    CHK(check_batch_invariant(m));
     const cmtts_config& c = m->cfg;
     const int C = c.res_channels, NL = c.res_layers, M = c.n_mels;
     hipStream_t s = (hipStream_t)stream;
@@ -2726,14 +2762,18 @@ static int vocoder_generator(cmtts_vocoder* v, const float* mel_ct, int B, int T
                                  (v->precision ? (pair16_pays && v->c1f[r][0][v->precision - 1] != nullptr) : v->c1f32[r][0] != nullptr);
             // fp32, C = 64, k >= 7, chip-filling launches (round 4): the pair as two Winograd launches (conv_xlw_kernel<64>: one wave per workgroup with both
             // m-tiles, eight workgroups per CU) instead of the fused pair kernel — 10 / 15 products per output pair instead of 14 / 22 outweigh xt's trip through HBM (k = 11: 2 x 1225 against 3217 us; k = 7: -0.3 ms per batch)
+            // the launch-size gate of the fp32 Winograd forms (here, qpair below, conv_xlq / conv_xlw through wino_force); vocoder option "batch_invariant":
+            // the large-launch branch at every size, so that a row's bits do not depend on the batch (every other size-dependent choice of this function —
+            // conv_xl's m-tile split "voc_xl_split", the generic conv's tile configurations, the upsamplers' phase split — only divides the same work)
+            const bool big_launch = v->batch_invariant || (long)((To + 63) / 64) * B >= 1024;
             const bool xw64 = g_voc_wino64 && g_voc_wino && v->winograd && !v->precision && co == 64 && rk >= g_voc_wino64_k && v->c1w32[r][0] && v->c2w32[r][0] &&
-                              (g_voc_wino == 2 || (long)((To + 63) / 64) * B >= 1024);
+                              (g_voc_wino == 2 || big_launch);
             if (xw64) pair_ok = false;
             // round 6: k = 3 pairs at C = 64 / 128 with both convs in the F(4,3) form and xt kept on the CU (conv_xlq_pair.hip): at C = 128 the two conv_xlq
             // launches below without xt's trip through HBM and the residual's second read (five tensor passes -> two; the same products on quads one frame apart: fp32
             // Winograd rounding between the two); at C = 64 half the MFMAs of the direct pair kernel.  64.4 -> 62.9 ms per 32 x 512-frame batch
             bool qpair = g_voc_qpair && g_voc_wino && g_voc_wino43 && v->winograd && !v->precision && rk == 3 && (co == 64 || co == 128) &&
-                         (g_voc_qpair == 2 || g_voc_wino == 2 || (long)((To + 63) / 64) * B >= 1024);
+                         (g_voc_qpair == 2 || g_voc_wino == 2 || big_launch);
             for (int mi = 0; mi < 3 && qpair; ++mi) qpair = v->c1q32[r][mi] && v->c2q32[r][mi];
             for (int mi = 0; mi < 3 && qpair; ++mi) {
                 const bool lastm = mi == 2;
@@ -2783,7 +2823,7 @@ static int vocoder_generator(cmtts_vocoder* v, const float* mel_ct, int B, int T
                     // round 4: the Winograd form of both convs (conv_xlw_kernel: 4 / 10 / 15 products per output pair instead of 6 / 14 / 22)
                     const bool xw = g_voc_wino && v->winograd && v->c1w32[r][mi] && v->c2w32[r][mi];
                     xa.x = xr; xa.y = bT; xa.wf = xw ? v->c1w32[r][mi] : v->c1f32[r][mi]; xa.bias = v->c1[r][mi].bias;
-                    xa.bstride = cs; xa.B = B; xa.C = co; xa.T = To; xa.ld = ld; xa.k = rk; xa.dil = dil; xa.slope = 0.1f; xa.wino_force = g_voc_wino == 2;
+                    xa.bstride = cs; xa.B = B; xa.C = co; xa.T = To; xa.ld = ld; xa.k = rk; xa.dil = dil; xa.slope = 0.1f; xa.wino_force = g_voc_wino == 2 || v->batch_invariant;
                     // round 5: dilation-1 convs (every conv2, conv1 of the first pair) in the F(4,3) form (conv_xlq_kernel: 6 / 16 / 24 products per quad of outputs where
                     // the F(2,3) tap groups take 8 / 20 / 30); -2 = launch too small or shape not covered: the F(2,3) form, then the direct one
                     int rc1 = -2;
@@ -3046,6 +3086,7 @@ int cmtts_model_set_option(cmtts_model* m, const char* name, int value) {
         {"ffn2_split", &m->ffn2_split, 0, 1},            // FFN linear of the FFT blocks as 8 K-segment partial GEMMs + one reduction (1) or one launch (0)
         {"text16", &m->text16, 0, 1},                    // bf16 / fp16 models: 16-bit operands in the FFT blocks' FFN contractions as well (default 0)
         {"winograd", &m->winograd, 0, 2},                // fp32 persistent denoiser stack: the gated k = 3 conv as Winograd F(4,3) (default 1), F(2,3) (2) or in the direct form (0: bitwise the per-layer kernels)
+        {"batch_invariant", &m->batch_invariant, 0, 1},  // fp32, winograd = 1: the per-layer residual blocks of small batches in the stack's F(4,3) form too (default 0)
     };
     bool found;
     const int prev = knob_set(tab, sizeof(tab) / sizeof(tab[0]), name, value, &found);
@@ -3058,6 +3099,7 @@ int cmtts_vocoder_set_option(cmtts_vocoder* v, const char* name, int value) {
     const Knob tab[] = {
         {"ups16", &v->ups16, 0, 1},                      // 16-bit modes: 16-bit operands in the upsamplers too (1) or fp32 upsamplers (0)
         {"winograd", &v->winograd, 0, 1},                // fp32 generator: the ResBlock convs of the C >= 128 stages in their Winograd form (default 1; 0 = the direct form)
+        {"batch_invariant", &v->batch_invariant, 0, 1},  // fp32 generator: the large-launch forms at every launch size (default 0)
     };
     bool found;
     const int prev = knob_set(tab, sizeof(tab) / sizeof(tab[0]), name, value, &found);

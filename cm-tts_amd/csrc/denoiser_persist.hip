@@ -26,6 +26,7 @@
 #include "gate.h"
 #include "persist_args.h"
 #include "persist_tail.h"
+#include "wino43.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -374,19 +375,8 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
                 Da = *reinterpret_cast<const f32x4*>(rr);
                 Db = *reinterpret_cast<const float2*>(rr + 4);
             };
-            // (written on float pairs: the compiler then issues v_pk_fma_f32 / v_pk_add_f32 — 8 VALU operations per k-step instead of 12 + moves;
-            //  the same fused operations on the same values)
-            auto transform4 = [&]() {
-                const f32x2 P01 = {Da[0], Da[1]}, P23 = {Da[2], Da[3]}, P45 = {Db.x, Db.y};
-                const f32x2 c4 = {4.f, 4.f}, cm5 = {-5.f, -5.f}, c2 = {2.f, -2.f};
-                const f32x2 V05 = __builtin_elementwise_fma(c4, P01, __builtin_elementwise_fma(cm5, P23, P45));
-                const float t0 = __builtin_fmaf(-4.f, Da[2], Db.x), t1 = __builtin_fmaf(-4.f, Da[1], Da[3]);
-                const float t2 = Db.x - Da[2], t3 = Da[3] - Da[1];
-                const f32x2 a0 = {t0, t0}, a1 = {t1, -t1}, b0 = {t2, t2}, b1 = {t3, t3};
-                const f32x2 V12 = a0 + a1;
-                const f32x2 V34 = __builtin_elementwise_fma(c2, b1, b0);
-                V4[0] = V05.x; V4[1] = V12.x; V4[2] = V12.y; V4[3] = V34.x; V4[4] = V34.y; V4[5] = V05.y;
-            };
+            // (wino43.h: the input transform on float pairs, v_pk_fma_f32 / v_pk_add_f32 — shared with the per-layer form, resblock_split_w43.hip)
+            auto transform4 = [&]() { wino43::transform(Da, Db, V4); };
             load_d4(0);
 #pragma unroll 1
             for (int s0 = 0; s0 < NS4; s0 += WR4) {
@@ -550,30 +540,11 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
                 }
             // (on ROW PAIRS: registers r, r + 1 of an accumulator are adjacent, so the output transform's adds and the gate's multiplies / adds run as
             //  v_pk_*_f32 on two rows at once — the same operations on the same values, half the VALU instructions next to the other waves' MFMAs)
-            auto out4 = [&](int i, int h, f32x2 bias, f32x2 (&y)[4]) {
+            auto out4 = [&](int i, int h, f32x2 bias, f32x2 (&y)[4]) {      // wino43.h: the output transform
                 auto P = [&](int p) { return f32x2{acc4[i][p][2 * h], acc4[i][p][2 * h + 1]}; };
-                const f32x2 m0 = P(0), m1 = P(1), m2 = P(2), m3 = P(3), m4 = P(4), m5 = P(5);
-                const f32x2 s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-                const f32x2 c2 = {2.f, 2.f}, c4 = {4.f, 4.f}, c8 = {8.f, 8.f};
-                y[0] = ((m0 + s12) + s34) + bias;
-                y[1] = __builtin_elementwise_fma(c2, d34, d12) + bias;
-                y[2] = __builtin_elementwise_fma(c4, s34, s12) + bias;
-                y[3] = (__builtin_elementwise_fma(c8, d34, d12) + m5) + bias;
+                wino43::out_transform(P(0), P(1), P(2), P(3), P(4), P(5), bias, y);
             };
-            auto gate2 = [&](f32x2 g, f32x2 f) -> f32x2 {      // cmtts_gate (gate.h) on two elements: the same multiplies, v_exp / v_rcp, adds and fma per element
-                const f32x2 nl2e = {-1.44269504088896340736f, -1.44269504088896340736f}, l2e = {1.44269504088896340736f, 1.44269504088896340736f};
-                const f32x2 one = {1.f, 1.f}, m2c = {-2.f, -2.f};
-                const f32x2 ag = g * nl2e;
-                const f32x2 eg = {__builtin_amdgcn_exp2f(ag.x), __builtin_amdgcn_exp2f(ag.y)};
-                const f32x2 dg = one + eg;
-                const f32x2 sg = {__builtin_amdgcn_rcpf(dg.x), __builtin_amdgcn_rcpf(dg.y)};
-                const f32x2 af = (f + f) * l2e;
-                const f32x2 ef = {__builtin_amdgcn_exp2f(af.x), __builtin_amdgcn_exp2f(af.y)};
-                const f32x2 df = one + ef;
-                const f32x2 rf = {__builtin_amdgcn_rcpf(df.x), __builtin_amdgcn_rcpf(df.y)};
-                const f32x2 th = __builtin_elementwise_fma(m2c, rf, one);
-                return sg * th;
-            };
+            auto gate2 = [&](f32x2 g, f32x2 f) -> f32x2 { return wino43::gate2(g, f); };      // wino43.h: cmtts_gate (gate.h) on two elements
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb)
 #pragma unroll

@@ -17,6 +17,7 @@ struct ResArgs {
     float* z;             // split form only (resblock_split.hip): scratch [B][256][T] for the gated activations
     long long* dbg;       // optional [grid][8] cycle stamps written by wave 0 (phase timing, tools/phase_timing.py)
     unsigned* flag;       // optional pinned error word (16-bit kernel, fp16 mode): set to 3 when a conv input leaves the fp16 range
+    const float* u;       // F(4,3) form only (resblock_split_w43.hip): [B][256][T] u already formed (three-launch path), else nullptr
 };
 
 #ifdef __cplusplus
@@ -24,6 +25,8 @@ extern "C" {
 #endif
 int cmtts_launch_resblock(const ResArgs* a, void* stream);
 int cmtts_launch_resblock_split(const ResArgs* a, void* stream);         // fp32, two launches, small batches (needs a->z)
+int cmtts_launch_resblock_split_out(const ResArgs* a, void* stream);     // its second launch alone: projection + x' / skip epilogue from a->z
+int cmtts_launch_resblock_w43(const ResArgs* a, void* stream);           // fp32, the persistent stack's F(4,3) form as two launches (needs a->z)
 int cmtts_launch_resblock_lp(const ResArgs* a, int mode, void* stream);   // mode 1 = bf16, 2 = fp16 operands
 void cmtts_resblock_set_tile(int frames);   // 0 = automatic, 32 or 64 = forced frames per workgroup
 void cmtts_resblock_set_debug(long long* dbg);

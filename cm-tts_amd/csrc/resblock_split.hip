@@ -217,3 +217,14 @@ extern "C" int cmtts_launch_resblock_split(const ResArgs* ap, void* stream_) {
     hipLaunchKernelGGL(resblock_split_out_kernel, grid, dim3(64 * NWS), lds, stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
+
+// The second launch alone, behind another producer of a->z (resblock_split_w43.hip: the persistent stack's F(4,3) conv).
+extern "C" int cmtts_launch_resblock_split_out(const ResArgs* ap, void* stream_) {
+    const ResArgs& a = *ap;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!a.z || a.B <= 0 || a.T <= 0 || (long)C * a.T >= (1L << 31)) return -2;
+    const size_t lds = (size_t)C * U_LD * sizeof(float);
+    dim3 grid((a.T + FN - 1) / FN, a.B, MS);
+    hipLaunchKernelGGL(resblock_split_out_kernel, grid, dim3(64 * NWS), lds, stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}

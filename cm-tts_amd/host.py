@@ -187,7 +187,10 @@ class CMTotalTTS(torch.nn.Module):
         models: the in- / out-projections and FFN contractions of the FFT blocks and the variance predictors' convs with 16-bit operands as well (the integer stages — durations, pitch buckets, lengths —
         then depend on the precision mode); "winograd" 1 (default) | 2 | 0 — fp32 models, large batches: the gated k = 3 conv of the persistent
         denoiser stack as a Winograd convolution — 1: F(4,3) (half of the conv's MFMAs; fp32 rounding differences ~8e-6 on a mel; since round 5 / ABI revision 5),
-        2: F(2,3) (2/3 of them; ~4e-6) — or (0) in the direct form (bit for bit the per-layer kernels of small batches).  Returns the previous value."""
+        2: F(2,3) (2/3 of them; ~4e-6) — or (0) in the direct form (bit for bit the per-layer kernels of small batches); "batch_invariant" 0 (default) | 1 —
+        fp32 models with "winograd" 1: the per-layer residual blocks of small batches run the persistent stack's F(4,3) form too, so an utterance's mel
+        does not depend on what it is batched with (no effect with "winograd" 0 or on 16-bit models; with "winograd" 2 the denoiser calls raise:
+        F(2,3) has no per-layer form).  Returns the previous value."""
         prev = self.lib.cmtts_model_set_option(self._h, name.encode() if isinstance(name, str) else name, int(value))
         if prev < 0:
             _lib.check(prev)
@@ -777,7 +780,8 @@ class Generator(torch.nn.Module):
     def set_option(self, name, value):
         """Per-vocoder numerics option (cmtts_vocoder_set_option): "ups16" 1 (default) | 0 — in the 16-bit modes the upsamplers
         take 16-bit operands too, or stay fp32.  Returns the previous value.  "winograd" 1 (default) | 0 — fp32 generator, large batches: the ResBlock convs of the C >= 128 stages as Winograd
-        convolutions (4 / 10 / 15 products per output pair instead of 6 / 14 / 22; <= 1.2e-6 on the waveform) or in the direct form."""
+        convolutions (4 / 10 / 15 products per output pair instead of 6 / 14 / 22; <= 1.2e-6 on the waveform) or in the direct form.  "batch_invariant"
+        0 (default) | 1 — fp32 generator: the large-launch forms at every launch size, so a row's waveform does not depend on the batch."""
         prev = self.lib.cmtts_vocoder_set_option(self._h, name.encode() if isinstance(name, str) else name, int(value))
         if prev < 0:
             _lib.check(prev)

@@ -62,9 +62,11 @@ const char* cmtts_version(void);
  * the F(4,3) form since then and 2 the F(2,3) form that 1 used to select, and cmtts_poll_error's codes 2 / 3 no longer fail the next launch);
  * 6 — entry points only: the text-state records (cmtts_text_state_*) and cmtts_exchange_records of a sharded synthesis;
  * 7 — entry points only: windowed vocoding for streamed PCM (cmtts_vocoder_halo_frames, cmtts_vocoder_windows_workspace_bytes,
- * cmtts_vocoder_forward_windows).  A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
+ * cmtts_vocoder_forward_windows);
+ * 8 — options only: cmtts_model_set_option / cmtts_vocoder_set_option "batch_invariant" (a host detects support here).
+ * A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
  * against before it passes a struct (cmtts_amd/_lib.py does at load time). */
-#define CMTTS_ABI_VERSION 7
+#define CMTTS_ABI_VERSION 8
 int cmtts_abi_version(void);
 
 /* ---- weight import: replaces torch.load + load_state_dict (synthesize.py:79-83).
@@ -345,6 +347,16 @@ int cmtts_set_option(const char* name, int value);
  *       one network evaluation, ~8e-6 / ~4e-6 on a T = 4 mel, all equally far from a float64 evaluation at ordinary activation scales
  *       (tests/test_gpu_precision.py; F(4,3) loses a decimal digit on conv inputs of ~6e4); with 1 or 2 an utterance's low-order bits depend on
  *       whether its batch takes the persistent stack.
+ *   cmtts_model_set_option(m, "batch_invariant", 0 (default) | 1): fp32 models with "winograd" = 1: the residual layers of batches too small
+ *       for the persistent stack (every per-layer route: fused, split, three-launch, the set-aside groups of cmtts_sample_ragged,
+ *       cmtts_set_persistent_denoiser(0)) run the stack's F(4,3) form as well (csrc/resblock_split_w43.hip), bit for bit the stack's arithmetic:
+ *       an utterance's mel no longer depends on what it was batched with, at the per-layer kernels' latency.  No effect with "winograd" = 0
+ *       (every batch already takes the direct form) or on 16-bit models (one form at every shape).  With "winograd" = 2 (F(2,3), which has no
+ *       per-layer form) every denoiser call (cmtts_denoiser_forward, cmtts_sample*, cmtts_sample_ragged) returns CMTTS_E_UNSUPPORTED
+ *       before it launches anything.
+ *   cmtts_vocoder_set_option(v, "batch_invariant", 0 (default) | 1): fp32 generator: every form choice that depends on the launch size takes
+ *       its large-launch branch at every size (the Winograd ResBlock convs of "winograd" = 1 included), so that a row's waveform and int16 PCM
+ *       do not depend on the batch; large launches are unchanged.  No effect on the 16-bit modes.
  *   cmtts_vocoder_set_option(v, "winograd", 1 (default) | 0): fp32 generator, launches of >= 1024 column tiles (large batches): the k = 3 / 7 / 11
  *       ResBlock convs of the C = 256 and C = 128 stages and the k = 7 / 11 ResBlock convs of the C = 64 stage (hifigan/models.py:96-103) as Winograd convolutions — since round 5
  *       over QUADS of outputs one dilation apart, groups of three taps as F(4,3): 6 / 16 / 24 fp32 products per quad instead of 12 / 28 / 44 (csrc/conv_xlq.hip; dilation 1 and 3, dilation 5 at
