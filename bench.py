@@ -8,9 +8,13 @@ the sampler's noise drawn on the device inside the step (as the reference draws 
 runs its own batch (weak scaling, utterances shard with no data-path collective) and the step ends
 with the single RCCL all-gather that collates the mels.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement) carrying, besides the
-headline value, `roofline` (dominant kernel: gated k=3 Conv1D of the denoiser block, timed live with
-HIP events on its launch stream) and `cpu_baseline` (the numpy oracle timed on the host cores).
+Prints ONE JSON line on rank 0 carrying, besides the headline value, `roofline` (dominant kernel: gated
+k=3 Conv1D of the denoiser block, timed live with HIP events on its launch stream inside the timed steps).
+
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the
+line.  `--full` adds everything that takes runs of its own: `extras` (other sampler step counts, precisions,
+sizes and BASELINE configs, end-to-end wav, the vocoder alone; the N-GPU configs[3] / [4] blocks), `roofline_16bit`
+and `cpu_baseline` (the numpy oracle timed on the host cores).
 """
 import argparse
 import ctypes as C
@@ -22,6 +26,7 @@ import time
 # CPU-baseline hygiene: OpenMP worker i stays on core i for the whole run (set before torch creates
 # its thread pool), so the host-side timing does not depend on where the scheduler happens to move the workers
 # — single-process runs only: under torch.distributed.run every rank would bind its initial thread to the same first core.
+# Set with or without --full: the binding also places the thread that issues the timed steps, which must not move between the two.
 if os.environ.get("WORLD_SIZE", "1") == "1":
     os.environ.setdefault("OMP_PROC_BIND", "close")
     os.environ.setdefault("OMP_PLACES", "cores")
@@ -582,8 +587,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure extras, roofline_16bit and cpu_baseline (each in runs of its own)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out extras and roofline_16bit")
     ap.add_argument("--unfused", action="store_true", help="three-launch residual block (A/B)")
     ap.add_argument("--per-layer", action="store_true", help="one fused launch per residual layer instead of the persistent stack (A/B)")
     ap.add_argument("--tile", type=int, default=0, help="frames per workgroup of the fused residual block (tuning)")
@@ -782,12 +789,14 @@ def main():
                          "the same time: with the Winograd form the kernel issues only 1/2 (F(4,3)) or 2/3 (F(2,3)) of the conv's multiplies, so `algorithmic_frac` can exceed "
                          "1.0 without the hardware exceeding its peak (`algorithmic_speedup` = direct-form / issued FLOPs)"})
 
-    if (world > 1 or gather or os.environ.get("CMTTS_MULTI_EXTRAS") == "1") and not args.no_extras:      # gather: CMTTS_FORCE_COLLECTIVE=1 on one GPU
+    # ---- --full only: everything below runs after the headline's timed steps and dump, in runs of its own
+    extras_on = args.full and not args.no_extras
+    if (world > 1 or gather or os.environ.get("CMTTS_MULTI_EXTRAS") == "1") and extras_on:      # gather: CMTTS_FORCE_COLLECTIVE=1 on one GPU
         # every rank takes part: T = 1 / 2, configs[3] and configs[4] with their collectives (whole-job aggregates)
         result["extras"] = multi_gpu_extras(args, cfg, model, step, lambda f, k, w: timed(f, k, w, world, flush=flush), state,
                                             frames_rank, audio_s, rank, world, device, gather)
         flush()
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras_on:
         extras = result.get("extras", {})
         for n in (1, 2):
             k = max(4, args.steps // 2)
@@ -996,7 +1005,7 @@ def main():
                      "C = 128 pairs sit at the bf16 ridge (451 FLOP/B at k = 11 against 2.5 PF / 5 TB/s = 500), the narrow stages are "
                      "bound by per-conv fixed costs: profiles/r03_16bit_paths.md"}]
         result["extras"] = extras
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(cfg, sd)
         result["cpu_baseline"]["host_cores"] = os.cpu_count()
         result["cpu_baseline"]["cpu_quota_cores"] = cpu_quota_cores()

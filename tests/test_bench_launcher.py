@@ -25,6 +25,14 @@ def test_plain_invocation_launches_two_ranks():
     assert out["n_gpus"] == 2 and out["requested"] == 2
 
 
+def test_full_reaches_every_rank():
+    # the launcher hands its argv to the ranks unchanged: each one parses --full (the flag of the extras, roofline_16bit and cpu_baseline)
+    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full"], {"CMTTS_BENCH_DRYRUN": "1"})
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and json.loads(lines[0])["n_gpus"] == 2, r.stdout
+
+
 def test_world_size_mismatch_is_refused():
     # the launcher's world size must BE --gpus: a mislabelled number is worse than none
     r = _run(["--gpus", "4"], {"CMTTS_BENCH_DRYRUN": "1", "WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})

@@ -2,7 +2,7 @@
 set -x
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04w2; mkdir -p $O
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 V="env VP=fp32 VSTREAMS=0 VPAIR=1 VN=3 python tools/voc_prof.py"
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/vs -o v --output-format csv -- $V > /dev/null 2>&1
 python tools/kernel_stats_md.py $O/vs > $O/voc_fp32_kernel_stats.md

@@ -2,7 +2,7 @@
 set -x
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04w; mkdir -p $O
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/bstats -o b --output-format csv -- python bench.py --steps 10 --warmup 2 --no-extras --no-cpu-baseline > $O/bench_profiled.json 2> $O/bench_profiled.err
 python tools/kernel_stats_md.py $O/bstats --steps 12 > $O/bench_kernel_stats.md
 python tools/step_timeline.py $O/bstats > $O/bench_step_timeline.txt 2>&1
@@ -22,6 +22,6 @@ WINO=0 timeout 100 python tools/persist_timing.py > $O/persist_timing_direct.txt
 timeout 300 python tools/latency_bench.py > $O/latency.txt 2>&1
 timeout 300 python tools/ragged_bench.py > $O/ragged.txt 2>&1
 timeout 900 python tools/config_bench.py > $O/configs.txt 2>&1
-CMTTS_FORCE_COLLECTIVE=1 CMTTS_MULTI_EXTRAS=1 timeout 900 python bench.py --steps 10 --no-cpu-baseline > $O/bench_collective.json 2> $O/bench_collective.err
+CMTTS_FORCE_COLLECTIVE=1 CMTTS_MULTI_EXTRAS=1 timeout 900 python bench.py --full --steps 10 --no-cpu-baseline > $O/bench_collective.json 2> $O/bench_collective.err
 rm -rf $O/bstats $O/bf $O/bw $O/bm $O/bc
 ls $O

@@ -19,7 +19,7 @@ python tools/pmc_clock_md.py $O/bc > $O/bench_clock.md 2>&1
 python tools/pmc_update_json.py denoiser_persist_kernel_wino43 "denoiser_persist_kernel<false, false, true, 2>" $O/bench_hbm.md $O/bench_mfma.md $O/bench_clock.md $COMMIT \
   "round 5: FACT + F(4,3) 8-wave instance (WINO == 2), the default fp32 stack" > $O/pmc_entry.json 2>&1
 cp profiles/pmc_traffic.json $O/pmc_traffic.json
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 FACT=1 WINO=3 timeout 100 python tools/persist_timing.py > $O/persist_timing_wino43.txt 2>&1
 FACT=1 WINO=1 timeout 100 python tools/persist_timing.py > $O/persist_timing_wino.txt 2>&1
 timeout 900 python tools/config_bench.py > $O/configs.txt 2>&1
