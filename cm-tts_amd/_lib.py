@@ -29,6 +29,11 @@ class VarianceControlsStruct(C.Structure):
                 ("cwt_spec", C.c_void_p), ("f0_mean", C.c_void_p), ("f0_std", C.c_void_p), ("uv", C.c_void_p)]
 
 
+class ControlTablesStruct(C.Structure):
+    """struct cmtts_control_tables (include/cmtts_hip.h): fp32 [B, ld] device pointers as void*."""
+    _fields_ = [("d", C.c_void_p), ("e", C.c_void_p), ("p", C.c_void_p), ("ld", C.c_int)]
+
+
 class SampleGroupStruct(C.Structure):
     """struct cmtts_sample_group (include/cmtts_hip.h)."""
     _fields_ = [("noise", C.c_void_p), ("cond_ct", C.c_void_p), ("speaker_emb", C.c_void_p), ("B", C.c_int32), ("T", C.c_int32),
@@ -51,6 +56,7 @@ SIGNATURES = {
     "cmtts_text_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_text_forward_ragged": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_set_variance_controls": (_i, [_vp, C.POINTER(VarianceControlsStruct)]),
+    "cmtts_set_control_tables": (_i, [_vp, C.POINTER(ControlTablesStruct)]),
     "cmtts_frame_workspace_bytes": (_sz, [_vp, _i, _i]),
     "cmtts_frame_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_frame_forward_sub": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

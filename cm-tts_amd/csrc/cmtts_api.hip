@@ -708,6 +708,7 @@ struct cmtts_model {
     int batch_invariant = 0;                // fp32, winograd = 1: the per-layer residual blocks in the persistent stack's F(4,3) form (cmtts_model_set_option "batch_invariant")
     int ffn2_split = 1;    // FFT blocks: the FFN linear as 8 partial GEMMs over K segments + one reduction (another fp32 summation order than one launch: a property of the model handle, cmtts_model_set_option)
     cmtts_variance_controls vc = {1.f, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    cmtts_control_tables ct = {nullptr, nullptr, nullptr, 0};      // per-phoneme control tables [B][ld] (cmtts_set_control_tables); a table replaces the scalar of its control
     Allocs al;
     float *embed = nullptr, *omega_h = nullptr, *omega_cwt = nullptr, *omega_res = nullptr;
     float *pe_h = nullptr, *pe_cwt = nullptr;   // sinusoid tables [PE_ROWS][C]
@@ -1130,7 +1131,7 @@ int finalize_model(cmtts_model* m) {
 // batch's values still do not depend on its size.
 constexpr int FFN2_SEG = 8;
 struct TextWs {
-    float *x, *h, *qk, *vt, *st, *o, *f, *part, *c1, *c2, *spk, *out1, *h128, *logd, *dround, *epred, *escaled;
+    float *x, *h, *qk, *vt, *st, *o, *f, *part, *c1, *c2, *spk, *out1, *h128, *logd, *dround, *epred, *escaled, *pctl;
     int* cum;
     int64_t *eidx, *mlen;
     size_t bytes;
@@ -1161,6 +1162,7 @@ TextWs carve_text(const cmtts_config& c, int B, int L, void* base) {
     w.eidx = cv.take<int64_t>((size_t)B * L);
     w.mlen = cv.take<int64_t>((size_t)B);
     w.escaled = cv.take<float>((size_t)B * L);      // energy prediction x control (behind everything else: the other offsets do not depend on it)
+    w.pctl = cv.take<float>((size_t)B * L);         // the pitch control table's rows (cmtts_set_control_tables): persistent state like cum — the frame side reads it, a text-state record carries it
     w.bytes = cv.off + 256;
     return w;
 }
@@ -1229,6 +1231,7 @@ DenWs carve_den(const cmtts_config& c, int B, int T, void* base) {
 struct EnergyHead {        // round 6: get_energy_embedding + the embedding add (model/modules.py:318-328,358-363) as the epilogue of the energy predictor's head (kernels.hip: ln_linear_kernel<1, true>)
     const float* xin; const float* e_target; float e_control; const float* bins; int nbins; const float* E; float* out1; int64_t* e_idx; float* e_scaled;
     bool done;
+    const float* e_table = nullptr;      // control table [B][T] in place of e_control (ln_linear_kernel<1, 2>)
 };
 int g_energy_head = 1;          // internal switch "energy_head": 1 = in the head's launch (same bits), 0 = energy_embed_kernel behind the join
 int g_pred_wino = 1;            // round 6: the frame-level pitch predictor's k = 5 convs as F(4,3) tap groups (conv_k5q.hip; NOT bitwise the direct form: fp32 Winograd rounding), at every launch size
@@ -1307,7 +1310,7 @@ int predictor(const Predictor& P, const float* in, int ld_in, int B, int T, int 
         ldc = ld;
         if (g_pred_head && eh && g_energy_head && O == 1 && li + 1 == P.convs.size() && w.cout == 256) {
             k_ln_linear_energy(cur, P.ln_g[li], P.ln_b[li], 1e-12f, P.lin_w, P.lin_b, out, ln_lens, out_lens, B, T, ld, eh->xin, eh->e_target, eh->e_control,
-                               eh->bins, eh->nbins, eh->E, eh->out1, eh->e_idx, eh->e_scaled, s);
+                               eh->bins, eh->nbins, eh->E, eh->out1, eh->e_idx, eh->e_scaled, s, eh->e_table);
             eh->done = true;
             return 0;
         }
@@ -1930,6 +1933,13 @@ int cmtts_text_forward_ragged(cmtts_model* m, const int64_t* texts, const int64_
     const cmtts_config& c = m->cfg;
     if (c.multi_speaker && c.n_speaker > 0 && !speakers) return fail(CMTTS_E_INVALID, "speakers (ids into the speaker_emb table) are required (model/cmtts.py:78)");
     if (c.multi_speaker && c.n_speaker <= 0 && !spker_embeds) return fail(CMTTS_E_INVALID, "Speaker embedding should not be None (model/cmtts.py:80)");
+    const cmtts_control_tables& ct = m->ct;
+    if ((ct.d || ct.e || ct.p) && ct.ld != L)
+        return fail(CMTTS_E_INVALID, "cmtts_text_forward: the control tables' row pitch ld must equal L (cmtts_set_control_tables)");
+    if (ct.d && d_control != 1.0f)
+        return fail(CMTTS_E_INVALID, "cmtts_text_forward: a duration table replaces d_control, which must then be 1");
+    if (ct.e && m->vc.e_control != 1.0f)
+        return fail(CMTTS_E_INVALID, "cmtts_text_forward: an energy table replaces e_control, which must then be 1");
     TextWs w = carve_text(c, B, L, text_ws);
     if (text_ws_bytes < w.bytes) return fail(CMTTS_E_WORKSPACE, "text workspace too small");
     hipStream_t s = (hipStream_t)stream;
@@ -1969,19 +1979,23 @@ int cmtts_text_forward_ragged(cmtts_model* m, const int64_t* texts, const int64_
     if (m->vc.d_target) {   // teacher-forced durations (model/modules.py:365-367)
         HIPCHK(hipMemcpyAsync(d_rounded, m->vc.d_target, (size_t)B * L * 4, hipMemcpyDeviceToDevice, s));
         k_cumsum_durations(m->vc.d_target, w.cum, mel_len, B, L, s);
+    } else if (ct.d) {      // per-phoneme duration factors (a target keeps its precedence)
+        k_durations_table(log_d, ct.d, d_rounded, w.cum, mel_len, B, L, s);
     } else {
         k_durations(log_d, d_control, d_rounded, w.cum, mel_len, B, L, s);
     }
+    // the pitch table is read on the frame side, which may run on another rank: its rows become part of the text-side state
+    if (ct.p) HIPCHK(hipMemcpyAsync(w.pctl, ct.p, (size_t)B * L * 4, hipMemcpyDeviceToDevice, s));
     if (enc_out_ct && !c.multi_speaker)
         k_copy_rows(enc_out_ct, L, w.x, Lp, L, (long)B * H, s);
     // energy predictor (unmasked, positions from x[...,0] != 0) -> bucketize -> embedding add
     k_pos_embed_add(w.x, w.h, m->energy.alpha, m->omega_h, m->pe_h, PE_ROWS, B, H, L, Lp, se);
-    EnergyHead eh{w.x, m->vc.e_target, m->vc.e_control, m->energy_bins, c.energy_bins - 1, m->energy_emb, w.out1, e_idx, w.escaled, false};
+    EnergyHead eh{w.x, m->vc.e_target, m->vc.e_control, m->energy_bins, c.energy_bins - 1, m->energy_emb, w.out1, e_idx, w.escaled, false, ct.e};
     CHK(predictor(m->energy, w.h, Lp, B, L, Lp, pad_lens, pad_lens, ec1, ec2, e_pred, 1, se, t16mode, false, H == 256 ? &eh : nullptr));
     if (ss) CHK(branch_join(ss));
     if (!eh.done)
         k_energy_embed(w.x, e_pred, w.escaled, m->vc.e_target, m->vc.e_control, m->energy_bins, c.energy_bins - 1, m->energy_emb,
-                       w.out1, e_idx, B, H, L, Lp, s);
+                       w.out1, e_idx, B, H, L, Lp, s, ct.e);
     {   // cwt_predictor[0]: Linear(H -> cwt_hidden) (model/modules.py:204-205).  The reference applies it to the length-regulated frames;
         // a k = 1 contraction commutes with the gather (frame t copies phoneme mel2ph[t] - 1, a padding frame is W 0 + b = b), so it runs
         // over the L phonemes here and cmtts_frame_forward gathers its output: the same bits (tests/test_gpu_parity.py goldens,
@@ -1996,7 +2010,7 @@ int cmtts_text_forward_ragged(cmtts_model* m, const int64_t* texts, const int64_
         }
         if (rc != 0) CHK(launch(a, EPI_PLAIN, B, s));
     }
-    if (!m->vc.e_target && m->vc.e_control != 1.0f)     // the reference returns prediction * control (:326)
+    if (!m->vc.e_target && (ct.e || m->vc.e_control != 1.0f))     // the reference returns prediction * control (:326)
         HIPCHK(hipMemcpyAsync(e_pred, w.escaled, (size_t)B * L * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipGetLastError());
     return 0;
@@ -2034,6 +2048,11 @@ int cmtts_frame_forward_sub_t(cmtts_model* m, const void* text_ws, int B_all, in
     tw.out1 += (size_t)b0 * c.hidden * round_up(L_all, 4);
     tw.h128 += (size_t)b0 * c.cwt_hidden * round_up(L_all, 4);
     tw.cum += (size_t)b0 * L_all;
+    tw.pctl += (size_t)b0 * L_all;
+    if (m->ct.p && m->ct.ld != L_all)
+        return fail(CMTTS_E_INVALID, "cmtts_frame_forward: the control tables' row pitch ld must equal L_all (cmtts_set_control_tables)");
+    if (m->ct.p && m->vc.p_control != 1.0f)
+        return fail(CMTTS_E_INVALID, "cmtts_frame_forward: a pitch table replaces p_control, which must then be 1");
     FrameWs w = carve_frame(c, B, T, frame_ws);
     if (frame_ws_bytes < w.bytes) return fail(CMTTS_E_WORKSPACE, "frame workspace too small");
     hipStream_t s = (hipStream_t)stream;
@@ -2079,7 +2098,8 @@ int cmtts_frame_forward_sub_t(cmtts_model* m, const void* text_ws, int B_all, in
     if (!hp_done) k_pos_embed_add(w.h128, w.hp, m->cwt.alpha, m->omega_cwt, m->pe_cwt, PE_ROWS, B, CH, T, T, s);
     CHK(predictor(m->cwt, w.hp, T, B, T, T, nullptr, nullptr, w.c1, w.c2, cwt_out, O, s, (m->text16 && (m->precision == 1 || m->precision == 2)) ? m->precision : 0, true));
     if (ss) CHK(branch_join(ss));
-    if (m->vc.p_control != 1.0f) k_scale(cwt_out, cwt_out, (long)B * T * O, m->vc.p_control, s);   // :270
+    if (m->ct.p) k_pitch_table_scale(cwt_out, mel2ph, tw.cum, tw.pctl, B, O, L, T, s);      // :270 per phoneme: the rows the text side (or cmtts_text_state_unpack) left in the workspace
+    else if (m->vc.p_control != 1.0f) k_scale(cwt_out, cwt_out, (long)B * T * O, m->vc.p_control, s);   // :270
     if (m->vc.cwt_spec) {   // teacher-forced pitch: target spectrogram, statistics and uv (:379-390)
         k_pitch_index(m->vc.cwt_spec, 10, m->vc.f0_mean, m->vc.f0_std, 1, 1.0f, nullptr, 0, c.use_uv ? m->vc.uv : nullptr,
                       c.pitch_norm_eps, w.r, p_idx, f0_denorm, B, T, s);
@@ -2094,21 +2114,27 @@ int cmtts_frame_forward_sub_t(cmtts_model* m, const void* text_ws, int B_all, in
 }
 
 // ---- per-utterance text-side state records (text_state.hip): the regions of a text workspace that cmtts_frame_forward_sub reads —
-// out1 [H][Lp], h128 [cwt_hidden][Lp], spk [H] (fp32), cum [L] (int32) — behind a 64-byte header, each region 16-byte aligned.
+// out1 [H][Lp], h128 [cwt_hidden][Lp], spk [H] (fp32), cum [L] (int32), and with a pitch control table installed its rows pctl [L] (fp32) —
+// behind a 64-byte header, each region 16-byte aligned.
 namespace {
 struct TextStateLayout {
     long off[TEXT_STATE_MAX_REGIONS], bytes[TEXT_STATE_MAX_REGIONS], stride[TEXT_STATE_MAX_REGIONS];
     long rec_bytes;
+    int n_regions;
 };
-TextStateLayout text_state_layout(const cmtts_config& c, int L) {
+// with_p: a pitch control table is installed (cmtts_set_control_tables) — the record gains its row as a fifth region and names layout
+// revision 2; without one a record is byte for byte the revision-1 record
+TextStateLayout text_state_layout(const cmtts_config& c, int L, bool with_p) {
     const int Lp = round_up(L, 4);
     TextStateLayout t;
     t.bytes[0] = (long)c.hidden * Lp * 4;       // out1
     t.bytes[1] = (long)c.cwt_hidden * Lp * 4;   // h128
     t.bytes[2] = (long)c.hidden * 4;            // spk
     t.bytes[3] = (long)L * 4;                   // cum
+    t.bytes[4] = (long)L * 4;                   // pctl: the pitch control table's row (layout revision 2 only)
+    t.n_regions = with_p ? 5 : 4;
     long off = TEXT_STATE_HEADER_BYTES;
-    for (int g = 0; g < TEXT_STATE_MAX_REGIONS; ++g) {
+    for (int g = 0; g < t.n_regions; ++g) {
         t.stride[g] = t.bytes[g];               // per-utterance stride in the workspace: the regions are [B][...] slabs
         t.off[g] = off;
         off += (t.bytes[g] + 15) / 16 * 16;
@@ -2116,21 +2142,22 @@ TextStateLayout text_state_layout(const cmtts_config& c, int L) {
     t.rec_bytes = off;
     return t;
 }
-TextStateCopy text_state_args(const cmtts_config& c, void* ws, int B_all, int L, void* records, int n, int unpack) {
-    const TextStateLayout t = text_state_layout(c, L);
+TextStateCopy text_state_args(const cmtts_config& c, void* ws, int B_all, int L, void* records, int n, int unpack, bool with_p) {
+    const TextStateLayout t = text_state_layout(c, L, with_p);
     TextWs tw = carve_text(c, B_all, L, ws);
-    char* base[TEXT_STATE_MAX_REGIONS] = {(char*)tw.out1, (char*)tw.h128, (char*)tw.spk, (char*)tw.cum};
+    char* base[TEXT_STATE_MAX_REGIONS] = {(char*)tw.out1, (char*)tw.h128, (char*)tw.spk, (char*)tw.cum, (char*)tw.pctl};
     TextStateCopy a;
     memset(&a, 0, sizeof(a));
     int chunks = 0;
-    for (int g = 0; g < TEXT_STATE_MAX_REGIONS; ++g) {
+    for (int g = 0; g < t.n_regions; ++g) {
         TextStateRegion& R = a.reg[g];
         R.ws = base[g]; R.ws_stride = t.stride[g]; R.rec_off = t.off[g]; R.bytes = t.bytes[g];
         R.vec16 = ((uintptr_t)R.ws % 16 == 0 && R.ws_stride % 16 == 0 && R.bytes % 16 == 0 && (uintptr_t)records % 16 == 0) ? 1 : 0;
         R.chunk0 = chunks;
         chunks += (int)((R.bytes + TEXT_STATE_CHUNK - 1) / TEXT_STATE_CHUNK);
     }
-    a.n_regions = TEXT_STATE_MAX_REGIONS; a.n_chunks = chunks; a.unpack = unpack;
+    a.n_regions = t.n_regions; a.n_chunks = chunks; a.unpack = unpack;
+    a.layout = with_p ? TEXT_STATE_LAYOUT_P : TEXT_STATE_LAYOUT;
     a.n = n; a.B_all = B_all; a.L_all = L; a.hidden = c.hidden; a.cwt_hidden = c.cwt_hidden;
     a.rec = (char*)records; a.rec_bytes = t.rec_bytes;
     a.cum = tw.cum;
@@ -2140,7 +2167,7 @@ TextStateCopy text_state_args(const cmtts_config& c, void* ws, int B_all, int L,
 
 size_t cmtts_text_state_record_bytes(const cmtts_model* m, int L_all) {
     if (!m || L_all <= 0) return 0;
-    return (size_t)text_state_layout(m->cfg, L_all).rec_bytes;
+    return (size_t)text_state_layout(m->cfg, L_all, m->ct.p != nullptr).rec_bytes;
 }
 
 int cmtts_text_state_pack(cmtts_model* m, const void* text_ws, int B_all, int L_all, const int32_t* rows, int n, const int64_t* global_idx,
@@ -2149,7 +2176,9 @@ int cmtts_text_state_pack(cmtts_model* m, const void* text_ws, int B_all, int L_
     if (!text_ws || !records || (n > 0 && !rows) || B_all <= 0 || L_all <= 0 || n < 0)
         return fail(CMTTS_E_INVALID, "cmtts_text_state_pack: bad argument");
     if ((uintptr_t)records % 16) return fail(CMTTS_E_INVALID, "cmtts_text_state_pack: records must be 16-byte aligned");
-    TextStateCopy a = text_state_args(m->cfg, const_cast<void*>(text_ws), B_all, L_all, records, n, 0);
+    if (m->ct.p && m->ct.ld != L_all)
+        return fail(CMTTS_E_INVALID, "cmtts_text_state_pack: the control tables' row pitch ld must equal L_all (cmtts_set_control_tables)");
+    TextStateCopy a = text_state_args(m->cfg, const_cast<void*>(text_ws), B_all, L_all, records, n, 0, m->ct.p != nullptr);
     a.rows = rows; a.index = global_idx; a.src_lens = src_lens;
     if (cmtts_launch_text_state_copy(&a, stream) != 0) return fail(CMTTS_E_HIP, "text-state pack launch failed");
     return 0;
@@ -2160,7 +2189,9 @@ int cmtts_text_state_unpack(cmtts_model* m, const void* records, int n, int L_al
     if (!text_ws || !records || n <= 0 || L_all <= 0) return fail(CMTTS_E_INVALID, "cmtts_text_state_unpack: bad argument");
     if ((uintptr_t)records % 16) return fail(CMTTS_E_INVALID, "cmtts_text_state_unpack: records must be 16-byte aligned");
     if (text_ws_bytes < carve_text(m->cfg, n, L_all, nullptr).bytes) return fail(CMTTS_E_WORKSPACE, "text workspace too small");
-    TextStateCopy a = text_state_args(m->cfg, text_ws, n, L_all, const_cast<void*>(records), n, 1);
+    if (m->ct.p && m->ct.ld != L_all)
+        return fail(CMTTS_E_INVALID, "cmtts_text_state_unpack: the control tables' row pitch ld must equal L_all (cmtts_set_control_tables)");
+    TextStateCopy a = text_state_args(m->cfg, text_ws, n, L_all, const_cast<void*>(records), n, 1, m->ct.p != nullptr);
     if (cmtts_launch_text_state_copy(&a, stream) != 0) return fail(CMTTS_E_HIP, "text-state unpack launch failed");
     return 0;
 }
@@ -3207,6 +3238,16 @@ int cmtts_set_variance_controls(cmtts_model* m, const cmtts_variance_controls* v
     if (vc->cwt_spec && (!vc->f0_mean || !vc->f0_std || (m->cfg.use_uv && !vc->uv)))
         return fail(CMTTS_E_INVALID, "cmtts_set_variance_controls: a pitch target needs cwt_spec, f0_mean, f0_std (and uv)");
     m->vc = *vc;
+    return 0;
+}
+
+int cmtts_set_control_tables(cmtts_model* m, const cmtts_control_tables* t) {
+    if (!m) return fail(CMTTS_E_INVALID, "cmtts_set_control_tables: null model");
+    const cmtts_control_tables off = {nullptr, nullptr, nullptr, 0};
+    if (!t) t = &off;
+    if ((t->d || t->e || t->p) && t->ld <= 0)
+        return fail(CMTTS_E_INVALID, "cmtts_set_control_tables: ld (the row pitch = L of the next text-side call) must be > 0");
+    m->ct = *t;
     return 0;
 }
 

@@ -29,9 +29,16 @@ void k_dense_small(const float* in, long in_bs, long in_ks, const float* Wt, con
                    const float* add, float* out, int B, int K, int N, int act, hipStream_t s);
 void k_energy_embed(const float* x, const float* e_pred, float* e_scaled, const float* e_target, float e_control,
                     const float* bins, int nbins, const float* E, float* out1, int64_t* e_idx, int B, int C, int L, int ld,
-                    hipStream_t s);
+                    hipStream_t s, const float* e_table = nullptr);
 void k_durations(const float* logd, float d_control, float* d_rounded, int* cum, int64_t* mel_len,
                  int B, int L, hipStream_t s);
+// control tables [B][L] in place of the scalar (one factor per phoneme; e_table of k_energy_embed / k_ln_linear_energy likewise)
+void k_durations_table(const float* logd, const float* dtab, float* d_rounded, int* cum, int64_t* mel_len,
+                       int B, int L, hipStream_t s);
+void k_durations_table_serial(const float* logd, const float* dtab, float* d_rounded, int* cum, int64_t* mel_len,
+                              int B, int L, hipStream_t s);
+// cwt[b][t][:] *= ptab[b][mel2ph[b][t] - 1]; padding frames take the last frame's factor (k_scale's place when a pitch table is installed)
+void k_pitch_table_scale(float* cwt, const int64_t* mel2ph, const int* cum, const float* ptab, int B, int O, int L, int T, hipStream_t s);
 void k_durations_serial(const float* logd, float d_control, float* d_rounded, int* cum, int64_t* mel_len,
                  int B, int L, hipStream_t s);
 void k_broadcast_row(const float* row, float* out, int B, int n, hipStream_t s);      // out[b][:] = row[:]
@@ -43,7 +50,8 @@ void k_reduce_partials(const float* part, int nseg, const float* bias, const flo
 // ln_linear (O = 1) + bucketize + out1 = xin + energy_embedding[bucket] in one launch (the energy predictor's head; same bits as k_ln_linear + k_energy_embed)
 void k_ln_linear_energy(const float* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias, float* out,
                         const int64_t* ln_lens, const int64_t* out_lens, int B, int T, int ld, const float* xin, const float* e_target, float e_control,
-                        const float* bins, int nbins, const float* E, float* out1, int64_t* e_idx, float* e_scaled, hipStream_t s);
+                        const float* bins, int nbins, const float* E, float* out1, int64_t* e_idx, float* e_scaled, hipStream_t s,
+                        const float* e_table = nullptr);
 bool k_ln_linear(const float* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias, float* out,
                  const int64_t* ln_lens, const int64_t* out_lens, int B, int T, int ld, int O, hipStream_t s);
 void k_cumsum_durations(const float* dur, int* cum, int64_t* mel_len, int B, int L, hipStream_t s);

@@ -269,9 +269,12 @@ struct EnergyEpi {
     const float* E;         // energy_embedding.weight [nbins + 1][256]
     float* out1;            // [B][256][ld]
     int64_t* e_idx;         // [B][T]
-    float* e_scaled;        // [B][T]: prediction x control (written when control != 1 and no target)
+    float* e_scaled;        // [B][T]: prediction x control (written when control != 1 and no target; always with a table)
+    const float* e_table;   // [B][T] control table (EE == 2) or null: replaces e_control, one factor per position
 };
-template <int O, bool EE = false>
+// EE: 0 = no energy epilogue, 1 = with the scalar e_control, 2 = with the control table ee.e_table (an instance of its own: the
+// scalar instance stays the code it was)
+template <int O, int EE = 0>
 __global__ __launch_bounds__(256) void ln_linear_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float eps, const float* __restrict__ W,
                                                         const float* __restrict__ bias, float* __restrict__ out,
@@ -344,11 +347,12 @@ __global__ __launch_bounds__(256) void ln_linear_kernel(const float* __restrict_
         for (int o = 0; o < O; ++o) out[((long)b * T + t) * O + o] = keep ? acc[o] + bias[o] : 0.f;
     }
     if constexpr (EE) {
-        static_assert(!EE || O == 1, "energy head");
+        static_assert(EE == 0 || O == 1, "energy head");
         if (t < T) {      // all four quarter lanes of the column hold the prediction
             const float pred = keep ? acc[0] + bias[0] : 0.f;
             float v;
             if (ee.e_target) v = ee.e_target[(long)b * T + t];
+            else if constexpr (EE == 2) { v = pred * ee.e_table[(long)b * T + t]; if (q == 0) ee.e_scaled[(long)b * T + t] = v; }
             else { v = pred * ee.e_control; if (q == 0 && ee.e_control != 1.0f) ee.e_scaled[(long)b * T + t] = v; }
             int lo = 0, hi = ee.nbins;
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (ee.bins[mid] >= v) hi = mid; else lo = mid + 1; }
@@ -362,6 +366,11 @@ __global__ __launch_bounds__(256) void ln_linear_kernel(const float* __restrict_
             for (int i = 0; i < CQ; ++i) { xv[i] = xi[(long)i * ld]; ev[i] = e[i]; }
 #pragma unroll
             for (int i = 0; i < CQ; ++i) o1[(long)i * ld] = xv[i] + ev[i];
+        }
+        else if (t < ld) {   // the row's alignment columns T <= t < ld: defined (0), so that a text-state record of this row is defined bytes
+            float* o1 = ee.out1 + ((long)b * C + q * CQ) * ld + t;
+#pragma unroll
+            for (int i = 0; i < CQ; ++i) o1[(long)i * ld] = 0.f;
         }
     }
 }
@@ -493,16 +502,24 @@ __global__ __launch_bounds__(4 * SM_COLS) void stats_mlp_kernel(const float* __r
 // ---- energy bucketize + embedding add (model/modules.py:319-329,358-363); torch.bucketize
 // right=False = first i with bins[i] >= v
 constexpr int ENE_CG = 32;
+// e_table (optional, [B][L]): a control table in place of e_control — the scaled value is then always written
 __global__ void energy_embed_kernel(const float* x, const float* e_pred, float* e_scaled, const float* e_target,
                                     float e_control, const float* bins, int nbins, const float* E, float* out1,
-                                    int64_t* e_idx, int C, int L, int ld) {
+                                    int64_t* e_idx, int C, int L, int ld, const float* e_table) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
-    if (l >= L) return;
+    if (l >= L) {
+        if (l < ld) {        // the row's alignment columns: defined (0), like the fused head writes them
+            const int c0 = blockIdx.z * ENE_CG, c1 = min(C, c0 + ENE_CG);
+            for (int c = c0; c < c1; ++c) out1[((long)b * C + c) * ld + l] = 0.f;
+        }
+        return;
+    }
     // get_energy_embedding (model/modules.py:318-328): the target is bucketized when given, else
     // prediction * control (which is also what is returned as the prediction)
     float v;
     if (e_target) v = e_target[(long)b * L + l];
+    else if (e_table) { v = e_pred[(long)b * L + l] * e_table[(long)b * L + l]; if (blockIdx.z == 0) e_scaled[(long)b * L + l] = v; }
     else { v = e_pred[(long)b * L + l] * e_control; if (blockIdx.z == 0 && e_control != 1.0f) e_scaled[(long)b * L + l] = v; }
     int lo = 0, hi = nbins;
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (bins[mid] >= v) hi = mid; else lo = mid + 1; }
@@ -548,6 +565,49 @@ __global__ __launch_bounds__(64) void durations_wave_kernel(const float* logd, f
             d_rounded[(long)b * L + l] = d;
         }
         int v = (int)d;            // LengthRegulator.expand: int(expand_size)
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int n = __shfl_up(v, off);
+            if (lane >= off) v += n;
+        }
+        v += carry;
+        if (l < L) cum[(long)b * L + l] = v;
+        carry = __shfl(v, 63);
+    }
+    if (lane == 0) mel_len[b] = carry;
+}
+
+// ---- the same two kernels with a control TABLE dtab [B][L] in place of the scalar: d = clamp(round(exp(log_d) - 1) * dtab[b][l], 0)
+// (model/modules.py:369 is elementwise, so a per-phoneme factor is the same model).  Each lane loads its own factor beside its log_d:
+// the same multiply on the same operands as the scalar form when the table holds one value.
+__global__ void durations_table_kernel(const float* logd, const float* dtab, float* d_rounded, int* cum, int64_t* mel_len,
+                                       int B, int L) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int run = 0;
+    for (int l = 0; l < L; ++l) {
+        float d = rintf(expf(logd[(long)b * L + l]) - 1.0f) * dtab[(long)b * L + l];
+        d = d > 0.f ? d : 0.f;
+        d_rounded[(long)b * L + l] = d;
+        run += (int)d;
+        cum[(long)b * L + l] = run;
+    }
+    mel_len[b] = run;
+}
+__global__ __launch_bounds__(64) void durations_wave_table_kernel(const float* logd, const float* dtab, float* d_rounded, int* cum,
+                                                                  int64_t* mel_len, int L) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int carry = 0;
+    for (int l0 = 0; l0 < L; l0 += 64) {
+        const int l = l0 + lane;
+        float d = 0.f;
+        if (l < L) {
+            const float ld = logd[(long)b * L + l], f = dtab[(long)b * L + l];     // both loads issued before the exp
+            d = rintf(expf(ld) - 1.0f) * f;
+            d = d > 0.f ? d : 0.f;
+            d_rounded[(long)b * L + l] = d;
+        }
+        int v = (int)d;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
             const int n = __shfl_up(v, off);
@@ -834,6 +894,26 @@ __global__ void scale_kernel(const float* in, float* out, long n, float sc) {
     if (i < n) out[i] = in[i] * sc;
 }
 
+// ---- cwt[b][t][:] *= ptab[b][ph(b, t) - 1] (model/modules.py:270 with a per-phoneme factor): frame t takes the factor of the
+// phoneme the length regulator expanded it from; all O columns, the uv logit included, like the scalar.  A PADDING frame
+// (mel2ph = 0, t >= mel_len) takes the factor of the utterance's last frame: the f0 normalisation behind this kernel
+// (pitch_index_kernel, utils/pitch_tools.py cwt2f0_norm) takes its mean and deviation over all T padded frames, so what the padding
+// rows are scaled by reaches every valid frame — with this rule a row that holds one value gives the bits of the scalar p_control,
+// which scales the padding too.  An utterance without frames (mel_len = 0) takes its first factor.  In place; one lane per element.
+__global__ void pitch_table_scale_kernel(float* cwt, const int64_t* mel2ph, const int* cum, const float* ptab, int O, int L, int T) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;      // element of utterance b's [T][O] slab
+    const int b = blockIdx.y;
+    if (i >= T * O) return;
+    int64_t ph = mel2ph[(long)b * T + i / O];
+    if (ph <= 0) {                                            // padding: t >= mel_len, so frame mel_len - 1 exists below T
+        const int ml = cum[(long)b * L + L - 1];
+        ph = (ml > 0 && ml <= T) ? mel2ph[(long)b * T + ml - 1] : 1;
+    }
+    ph = ph < 1 ? 1 : (ph > L ? L : ph);
+    const long off = (long)b * T * O + i;
+    cwt[off] = cwt[off] * ptab[(long)b * L + (ph - 1)];
+}
+
 __global__ void fill_float_kernel(float* p, float v, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -898,15 +978,23 @@ bool k_stats_mlp(const float* in, long in_bs, long in_ks, const float* W0, const
 }
 void k_energy_embed(const float* x, const float* e_pred, float* e_scaled, const float* e_target, float e_control,
                     const float* bins, int nbins, const float* E, float* out1, int64_t* e_idx, int B, int C, int L, int ld,
-                    hipStream_t s) {
+                    hipStream_t s, const float* e_table) {
     // every channel slice reads the unscaled prediction; the scaled copy (returned as the prediction when a
     // control is set) is written to a second buffer and copied back afterwards
     hipLaunchKernelGGL(energy_embed_kernel, dim3(cdiv(L, 64), B, cdiv(C, ENE_CG)), dim3(64), 0, s, x, e_pred, e_scaled, e_target,
-                       e_control, bins, nbins, E, out1, e_idx, C, L, ld);
+                       e_control, bins, nbins, E, out1, e_idx, C, L, ld, e_table);
 }
 void k_durations(const float* logd, float d_control, float* d_rounded, int* cum, int64_t* mel_len, int B, int L,
                  hipStream_t s) {
     hipLaunchKernelGGL(durations_wave_kernel, dim3(B), dim3(64), 0, s, logd, d_control, d_rounded, cum, mel_len, L);
+}
+void k_durations_table(const float* logd, const float* dtab, float* d_rounded, int* cum, int64_t* mel_len, int B, int L,
+                       hipStream_t s) {
+    hipLaunchKernelGGL(durations_wave_table_kernel, dim3(B), dim3(64), 0, s, logd, dtab, d_rounded, cum, mel_len, L);
+}
+void k_durations_table_serial(const float* logd, const float* dtab, float* d_rounded, int* cum, int64_t* mel_len, int B, int L,
+                              hipStream_t s) {
+    hipLaunchKernelGGL(durations_table_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, logd, dtab, d_rounded, cum, mel_len, B, L);
 }
 void k_durations_serial(const float* logd, float d_control, float* d_rounded, int* cum, int64_t* mel_len, int B, int L,
                         hipStream_t s) {
@@ -925,9 +1013,13 @@ void k_reduce_partials(const float* part, int nseg, const float* bias, const flo
 // the energy predictor's head with the energy embedding in the same launch (EE instance)
 void k_ln_linear_energy(const float* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias, float* out,
                         const int64_t* ln_lens, const int64_t* out_lens, int B, int T, int ld, const float* xin, const float* e_target, float e_control,
-                        const float* bins, int nbins, const float* E, float* out1, int64_t* e_idx, float* e_scaled, hipStream_t s) {
-    const EnergyEpi ee{xin, e_target, e_control, bins, nbins, E, out1, e_idx, e_scaled};
-    hipLaunchKernelGGL((ln_linear_kernel<1, true>), dim3(cdiv(T, 64), B), dim3(256), 0, s, x, gamma, beta, eps, W, bias, out, ln_lens, out_lens, T, ld, ee);
+                        const float* bins, int nbins, const float* E, float* out1, int64_t* e_idx, float* e_scaled, hipStream_t s,
+                        const float* e_table) {
+    const EnergyEpi ee{xin, e_target, e_control, bins, nbins, E, out1, e_idx, e_scaled, e_table};
+    if (e_table)
+        hipLaunchKernelGGL((ln_linear_kernel<1, 2>), dim3(cdiv(T, 64), B), dim3(256), 0, s, x, gamma, beta, eps, W, bias, out, ln_lens, out_lens, T, ld, ee);
+    else
+        hipLaunchKernelGGL((ln_linear_kernel<1, 1>), dim3(cdiv(T, 64), B), dim3(256), 0, s, x, gamma, beta, eps, W, bias, out, ln_lens, out_lens, T, ld, ee);
 }
 bool k_ln_linear(const float* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias, float* out,
                  const int64_t* ln_lens, const int64_t* out_lens, int B, int T, int ld, int O, hipStream_t s) {
@@ -1025,6 +1117,9 @@ void k_copy_rows(float* dst, int dst_ld, const float* src, int src_ld, int width
 }
 void k_scale(const float* in, float* out, long n, float sc, hipStream_t s) {
     hipLaunchKernelGGL(scale_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, in, out, n, sc);
+}
+void k_pitch_table_scale(float* cwt, const int64_t* mel2ph, const int* cum, const float* ptab, int B, int O, int L, int T, hipStream_t s) {
+    hipLaunchKernelGGL(pitch_table_scale_kernel, dim3(cdiv(T * O, 256), B), dim3(256), 0, s, cwt, mel2ph, cum, ptab, O, L, T);
 }
 void k_fill_float(float* p, float v, int n, hipStream_t s) {
     hipLaunchKernelGGL(fill_float_kernel, dim3(cdiv(n, 64)), dim3(64), 0, s, p, v, n);

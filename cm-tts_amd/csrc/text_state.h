@@ -4,16 +4,17 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#define TEXT_STATE_MAX_REGIONS 4
+#define TEXT_STATE_MAX_REGIONS 5
 #define TEXT_STATE_HEADER_BYTES 64
-#define TEXT_STATE_LAYOUT 0x54530001u      // "TS", layout revision 1
+#define TEXT_STATE_LAYOUT 0x54530001u      // "TS", layout revision 1: out1, h128, spk, cum
+#define TEXT_STATE_LAYOUT_P 0x54530002u    // layout revision 2: revision 1 + the pitch control table's row fp32 [L_all] as a fifth region
 
 // The record header (64 bytes, first in every record).
 struct TextStateHeader {
     int64_t index;         // global utterance index
     int64_t mel_len;       // sum of the rounded durations (= cum[L_all - 1])
     int32_t src_len;
-    uint32_t layout;       // TEXT_STATE_LAYOUT
+    uint32_t layout;       // TEXT_STATE_LAYOUT, or TEXT_STATE_LAYOUT_P with a pitch control table
     int32_t L_all, hidden, cwt_hidden, n_regions;
     int32_t pad[6];
 };
@@ -33,6 +34,7 @@ struct TextStateCopy {
     TextStateRegion reg[TEXT_STATE_MAX_REGIONS];
     int n_regions, n_chunks;     // chunks per record (all regions)
     int unpack;                  // 0: workspace rows -> records (+ header), 1: records -> workspace rows 0..n-1
+    uint32_t layout;             // pack: the header's layout word
     int n, B_all, L_all, hidden, cwt_hidden;
     char* rec;                   // records [n][rec_bytes]
     long rec_bytes;

@@ -26,7 +26,7 @@ __global__ __launch_bounds__(TS_THREADS) void text_state_copy_kernel(TextStateCo
             h.index = a.index ? a.index[r] : row;
             h.mel_len = a.cum[(long)row * a.L_all + a.L_all - 1];
             h.src_len = a.src_lens ? (int32_t)a.src_lens[row] : -1;
-            h.layout = TEXT_STATE_LAYOUT;
+            h.layout = a.layout;
             h.L_all = a.L_all; h.hidden = a.hidden; h.cwt_hidden = a.cwt_hidden; h.n_regions = a.n_regions;
             *reinterpret_cast<TextStateHeader*>(rec) = h;
         }

@@ -38,6 +38,71 @@ def _i64(t, device):
     return t.to(device=device, dtype=torch.int64).contiguous()
 
 
+def _resolve_controls(B, L, p_control=1.0, e_control=1.0, d_control=1.0):
+    """The three prosody controls of a call over B utterances padded to L phonemes, each a Python number (the scalar path), a [B]
+    tensor (one factor per utterance) or a [B, L] tensor (one per phoneme), fp32.  Returns ((p, e, d) scalars, {"p" | "e" | "d":
+    fp32 [B, L] CPU table}): a control given as a tensor has scalar 1.0 and a table (a [B] vector broadcast along its row).
+    The tables are validated here, before anything launches — ValueError for a wrong type, dtype or shape, a NaN, p <= 0
+    (it also scales the uv logit) or d < 0."""
+    scal, tabs = [], {}
+    for name, v in (("p", p_control), ("e", e_control), ("d", d_control)):
+        if isinstance(v, np.ndarray):
+            v = torch.from_numpy(v)
+        if not isinstance(v, torch.Tensor):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+                raise ValueError(f"{name}_control: a number, a [B] tensor or a [B, L] tensor, not {type(v).__name__}")
+            scal.append(float(v))       # the scalar path, as it was: cmtts_set_variance_controls judges the value
+            continue
+        if v.dtype != torch.float32:
+            raise ValueError(f"{name}_control: the table must be float32, not {v.dtype}")
+        t = v.detach().to("cpu")
+        if t.dim() == 1 and t.shape[0] == B:
+            t = t[:, None].expand(B, L)
+        elif t.dim() != 2 or tuple(t.shape) != (B, L):
+            raise ValueError(f"{name}_control: shape {tuple(v.shape)}, expected [{B}] (per utterance) or [{B}, {L}] (per phoneme)")
+        if bool(torch.isnan(t).any()):
+            raise ValueError(f"{name}_control: NaN in the table")
+        if name == "p" and not bool((t > 0).all()):
+            raise ValueError("p_control: every factor must be > 0 (it also scales the uv logit)")
+        if name == "d" and not bool((t >= 0).all()):
+            raise ValueError("d_control: every factor must be >= 0")
+        tabs[name] = t.contiguous()
+        scal.append(1.0)
+    return tuple(scal), tabs
+
+
+def _check_no_scalar_with_table(scalars, p_control=None, e_control=None, d_control=None):
+    """A table REPLACES the scalar of its control (cmtts_set_control_tables): a per-call table on top of a configured scalar other
+    than 1 is refused instead of silently dropping one of the two."""
+    for name, sc, v in zip("ped", scalars, (p_control, e_control, d_control)):
+        if isinstance(v, (torch.Tensor, np.ndarray)) and not isinstance(sc, (torch.Tensor, np.ndarray)) and float(sc) != 1.0:
+            raise ValueError(f"{name}_control: a table replaces the scalar control, which is {sc} here (it must be 1)")
+
+
+class _InstalledTables:
+    """The control tables of one call on the device, installed on the model (cmtts_set_control_tables); clear() in a finally."""
+
+    def __init__(self, model, tabs, L, lo=None, hi=None, present_only=()):
+        self.model, self.keep = model, []
+        ct = _lib.ControlTablesStruct(ld=int(L))
+        for name, t in tabs.items():
+            if name in present_only:        # a frame-side rank: the rows come out of the records, only "p installed" matters
+                t = t[:1]
+            elif lo is not None:
+                t = t[lo:hi]
+            self.keep.append(t.to(device=model.device, dtype=torch.float32).contiguous())
+            setattr(ct, name, _ptr(self.keep[-1]))
+        self.active = bool(self.keep)
+        if self.active:
+            _lib.check(model.lib.cmtts_set_control_tables(model._h, C.byref(ct)))
+
+    def clear(self):
+        if self.active:
+            self.model.lib.cmtts_set_control_tables(self.model._h, None)
+            torch.cuda.current_stream(self.model.device).synchronize()      # the tables must outlive the kernels
+            self.active = False
+
+
 def _push_state_dict(lib, setter, handle, sd):
     for name, v in sd.items():
         if isinstance(v, torch.Tensor):
@@ -246,8 +311,16 @@ class DurationPitchSpeakerNet(torch.nn.Module):
                 p_control=1.0, e_control=1.0, d_control=1.0, max_mel_len=None, **kwargs):
         """p_targets = {"cwt_spec" [B,T,10], "f0_mean" [B], "f0_std" [B], "uv" bool [B,T]}, e_targets [B,L],
         d_targets [B,L] as in the reference.  `mel2phs` is accepted and ignored: mel2ph is recomputed from
-        d_targets (dur_to_mel2ph), which is what the reference's dataset stores."""
+        d_targets (dur_to_mel2ph), which is what the reference's dataset stores.
+        p_control / e_control / d_control: a number, or a float32 tensor [B] (one factor per utterance) or [B, L] (one per phoneme):
+        the tables of cmtts_set_control_tables (model/modules.py:270, 326, 369 are elementwise)."""
         o = self._owner
+        if texts is None:
+            o._require()
+        tshape = tuple(torch.as_tensor(texts).shape)
+        if len(tshape) != 2:
+            raise ValueError("texts must be [B, L]")
+        (p_control, e_control, d_control), tabs = _resolve_controls(tshape[0], tshape[1], p_control, e_control, d_control)
         o._require()
         cfg, lib, dev = o.config, o.lib, o.device
         vc, keep = None, []
@@ -292,7 +365,9 @@ class DurationPitchSpeakerNet(torch.nn.Module):
             tws = o._ws.get("text", nb, dev)
             if vc is not None:
                 _lib.check(lib.cmtts_set_variance_controls(o._h, C.byref(vc)))
+            inst = None
             try:
+                inst = _InstalledTables(o, tabs, L)
                 _lib.check(lib.cmtts_text_forward(o._h, _ptr(texts), _ptr(src_lens), _ptr(spk_in), _ptr(spk_ids), B, L, float(d_control),
                                                   _ptr(log_d), _ptr(d_rounded), _ptr(mel_len), _ptr(e_pred), _ptr(e_idx),
                                                   _ptr(enc_ct), _ptr(spk), _ptr(tws), nb, _stream()))
@@ -318,6 +393,8 @@ class DurationPitchSpeakerNet(torch.nn.Module):
                 _lib.check(lib.cmtts_frame_forward_sub_t(o._h, _ptr(tws), B, L, 0, B, T, _ptr(cond_ct), _ptr(mel2ph), _ptr(cwt),
                                                          _ptr(f0), _ptr(p_idx), _ptr(stats), _ptr(p1), _ptr(p1t), _ptr(fws), nf, _stream()))
             finally:
+                if inst is not None:
+                    inst.clear()
                 if vc is not None:
                     lib.cmtts_set_variance_controls(o._h, None)              # back to the inference defaults
                     torch.cuda.current_stream(dev).synchronize()             # targets must outlive the kernels
@@ -958,11 +1035,14 @@ def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_
 
 
 def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=None, speakers=None, n_steps=4, noise=None,
-                      chunk_frames=STREAM_CHUNK_FRAMES, generator=None, max_wav_value=32768.0):
+                      chunk_frames=STREAM_CHUNK_FRAMES, generator=None, max_wav_value=32768.0,
+                      p_control=1.0, e_control=1.0, d_control=1.0):
     """Text -> streamed PCM: the duration net and the T-step sampler exactly as CMTotalTTSSynthesize.synthesize runs them (noise
     [n_noise, B, 1, T, 80] drawn as x0 = randn, then randn_like(x0) per further step, unless given), then vocoder_infer_stream on
-    the mels trimmed to their predicted lengths.  Yields (utterance, sample_offset, pcm int16 numpy, is_last)."""
-    out = model.duration_pitch_energy_net(speakers=speakers, texts=texts, src_lens=src_lens, spker_embeds=spker_embeds)
+    the mels trimmed to their predicted lengths.  Yields (utterance, sample_offset, pcm int16 numpy, is_last).
+    p_control / e_control / d_control: numbers, [B] or [B, L] float32 tensors (DurationPitchSpeakerNet.forward)."""
+    out = model.duration_pitch_energy_net(speakers=speakers, texts=texts, src_lens=src_lens, spker_embeds=spker_embeds,
+                                          p_control=p_control, e_control=e_control, d_control=d_control)
     B, T, _ = out["cond"].shape
     cfg = model.config
     if n_steps not in (1, 2, 4):
@@ -1402,9 +1482,19 @@ class CMTotalTTSSynthesize:
         model.eval()
         return model, diffusion
 
-    def synthesize(self, batch):
-        """batch = (ids, raw_texts, speakers, texts, src_lens, max_src_len, spker_embeds) after to_device (:88-153)."""
+    def synthesize(self, batch, p_control=None, e_control=None, d_control=None):
+        """batch = (ids, raw_texts, speakers, texts, src_lens, max_src_len, spker_embeds) after to_device (:88-153).
+        The controls given at construction apply (numbers, or float32 [B] / [B, L] tensors); a control given here replaces the
+        constructor's for this call — a table on top of a constructor scalar other than 1 is a ValueError."""
         kw = {"speakers": batch[2], "texts": batch[3], "src_lens": batch[4], "spker_embeds": batch[-1]}
+        _check_no_scalar_with_table((self.p_control, self.e_control, self.d_control), p_control, e_control, d_control)
+        for name, own, given in (("p_control", self.p_control, p_control), ("e_control", self.e_control, e_control),
+                                 ("d_control", self.d_control, d_control)):
+            v = own if given is None else given
+            if isinstance(v, (torch.Tensor, np.ndarray)) or v != 1.0:      # the defaults leave the call as it was
+                kw[name] = v
+        tshape = tuple(torch.as_tensor(kw["texts"]).shape)
+        _resolve_controls(tshape[0], tshape[-1], kw.get("p_control", 1.0), kw.get("e_control", 1.0), kw.get("d_control", 1.0))
         out_dict = self.duration_pitch_energy_net(**kw)
         B, T, _ = out_dict["cond"].shape
         cfg = self.model.config
@@ -1480,17 +1570,29 @@ def utterance_noise(seed, index, n_noise, T, n_mels, device):
     return torch.randn(n_noise, 1, int(T), int(n_mels), generator=g, device=device)
 
 
-def text_state_records(model: CMTotalTTS, texts, src_lens, lo, hi, spker_embeds=None, speakers=None, d_control=1.0):
+def text_state_records(model: CMTotalTTS, texts, src_lens, lo, hi, spker_embeds=None, speakers=None, d_control=1.0,
+                       e_control=1.0, p_control=1.0):
     """Text side of utterances [lo, hi) of a batch padded to L_all = texts.shape[1] phonemes (the reference's batch padding,
     cmtts_text_forward), packed into text-state records.  Returns (records uint8 [hi - lo, R], mel_len int64 [hi - lo]) on the
-    model's device."""
+    model's device.  d_control / e_control / p_control: numbers, or float32 tensors [B] / [B, L_all] over the WHOLE batch (global
+    utterance index): rows [lo, hi) are the tables of this call; with a p_control table the records carry its rows (layout
+    revision 2) for the frame side.  A scalar e_control / p_control other than 1 is set with cmtts_set_variance_controls by the
+    caller around both phases (synthesize_sharded), not here."""
     o = model
+    L = int(texts.shape[1])
+    (p_s, e_s, d_control), tabs = _resolve_controls(int(texts.shape[0]), L, p_control, e_control, d_control)
+    if p_s != 1.0 or e_s != 1.0:
+        raise ValueError("text_state_records: scalar p_control / e_control are variance controls of both phases "
+                         "(cmtts_set_variance_controls around them, as synthesize_sharded does); pass tables or 1.0 here")
     o._require()
     cfg, lib, dev = o.config, o.lib, o.device
-    L = int(texts.shape[1])
-    R = lib.cmtts_text_state_record_bytes(o._h, L)
     n = hi - lo
     if n <= 0:
+        inst = _InstalledTables(o, tabs, L, present_only=tuple(tabs))
+        try:
+            R = lib.cmtts_text_state_record_bytes(o._h, L)
+        finally:
+            inst.clear()
         return torch.empty(0, R, dtype=torch.uint8, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
     tx = _i64(texts[lo:hi], dev)
     sl = _i64(src_lens[lo:hi], dev)
@@ -1508,26 +1610,53 @@ def text_state_records(model: CMTotalTTS, texts, src_lens, lo, hi, spker_embeds=
         mel_len = torch.empty(n, dtype=torch.int64, device=dev)
         nb = lib.cmtts_text_workspace_bytes(o._h, n, L)
         tws = o._ws.get("text_sharded", nb, dev)
-        _lib.check(lib.cmtts_text_forward(o._h, _ptr(tx), _ptr(sl), _ptr(spk_in), _ptr(ids), n, L, float(d_control),
-                                          None, None, _ptr(mel_len), None, None, None, None, _ptr(tws), nb, _stream()))
-        rows = torch.arange(n, dtype=torch.int32, device=dev)
-        gidx = torch.arange(lo, hi, dtype=torch.int64, device=dev)
-        records = torch.empty(n, R, dtype=torch.uint8, device=dev)
-        _lib.check(lib.cmtts_text_state_pack(o._h, _ptr(tws), n, L, _ptr(rows), n, _ptr(gidx), _ptr(sl), _ptr(records), _stream()))
+        inst = None
+        try:
+            inst = _InstalledTables(o, tabs, L, lo, hi)      # this rank's utterances, selected by global index
+            R = lib.cmtts_text_state_record_bytes(o._h, L)
+            _lib.check(lib.cmtts_text_forward(o._h, _ptr(tx), _ptr(sl), _ptr(spk_in), _ptr(ids), n, L, float(d_control),
+                                              None, None, _ptr(mel_len), None, None, None, None, _ptr(tws), nb, _stream()))
+            rows = torch.arange(n, dtype=torch.int32, device=dev)
+            gidx = torch.arange(lo, hi, dtype=torch.int64, device=dev)
+            records = torch.empty(n, R, dtype=torch.uint8, device=dev)
+            _lib.check(lib.cmtts_text_state_pack(o._h, _ptr(tws), n, L, _ptr(rows), n, _ptr(gidx), _ptr(sl), _ptr(records), _stream()))
+        finally:
+            if inst is not None:
+                inst.clear()
     return records, mel_len
 
 
-def frame_side_from_records(model: CMTotalTTS, groups, L_all, n_steps=4, seed=0, tail_frames=16, details=None):
+def frame_side_from_records(model: CMTotalTTS, groups, L_all, n_steps=4, seed=0, tail_frames=16, details=None, p_control=1.0):
     """groups: [(bucket, records uint8 [n, R], utterance ids [n], planned lengths [n])] (shard.two_phase).  Every group's records are
     unpacked into a text workspace of its own, its frame side runs with T = bucket, and ONE cmtts_sample_ragged call samples all
     groups (each utterance trimmed to its planned length + tail_frames) with utterance_noise(seed, id).  Returns [(mel [n, bucket, 80],
-    mel_len int64 [n])]; `details` (a list) receives one {"mel2ph", "p_idx", "ids"} per group."""
+    mel_len int64 [n])]; `details` (a list) receives one {"mel2ph", "p_idx", "cwt", "ids"} per group.
+    p_control: what the text side was given (a number, or a float32 tensor [B] / [B, L_all] over the whole batch).  A table's rows
+    arrive in the records (layout revision 2); here it only says that they do — every rank must agree on that, record sizes depend
+    on it.  A number other than 1 is the caller's cmtts_set_variance_controls around both phases (synthesize_sharded)."""
     from . import shard
     cfg, lib, dev = model.config, model.lib, model.device
+    p_tab = None
+    if isinstance(p_control, (torch.Tensor, np.ndarray)):
+        pt = torch.as_tensor(p_control)
+        if pt.dim() not in (1, 2) or (pt.dim() == 2 and int(pt.shape[1]) != int(L_all)):
+            raise ValueError(f"p_control: shape {tuple(pt.shape)}, expected [B] or [B, {int(L_all)}]")
+        _, tabs = _resolve_controls(int(pt.shape[0]), int(L_all), p_control)
+        p_tab = {"p": tabs["p"]}
     n_noise = 1 if n_steps == 1 else n_steps + 1
-    lay = shard.text_state_layout(cfg.hidden, cfg.cwt_hidden, L_all)
+    lay = shard.text_state_layout(cfg.hidden, cfg.cwt_hidden, L_all, with_p=p_tab is not None)
     p1_ld = (L_all + 3) // 4 * 4
     use_p1 = getattr(model, "_precision_mode", 0) == 0 and model._cond_factors
+    inst = _InstalledTables(model, p_tab or {}, L_all, present_only=("p",))
+    try:
+        return _frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, details, lay, p1_ld, use_p1, n_noise)
+    finally:
+        inst.clear()
+
+
+def _frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, details, lay, p1_ld, use_p1, n_noise):
+    from . import shard
+    cfg, lib, dev = model.config, model.lib, model.device
     sample_groups, lens = [], []
     with torch.cuda.device(dev):
         f = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
@@ -1544,7 +1673,8 @@ def frame_side_from_records(model: CMTotalTTS, groups, L_all, n_steps=4, seed=0,
             p1t = None if p1 is None else f(n, cfg.res_layers, p1_ld, cfg.res_channels)
             nf = lib.cmtts_frame_workspace_bytes(model._h, n, T)
             fws = model._ws.get(("frame_unpacked", k), nf, dev)
-            _lib.check(lib.cmtts_frame_forward_sub_t(model._h, _ptr(tws), n, L_all, 0, n, T, _ptr(cond_ct), _ptr(mel2ph), None, None,
+            cwt = f(n, T, cfg.cwt_out) if details is not None else None
+            _lib.check(lib.cmtts_frame_forward_sub_t(model._h, _ptr(tws), n, L_all, 0, n, T, _ptr(cond_ct), _ptr(mel2ph), _ptr(cwt), None,
                                                      _ptr(p_idx), None, _ptr(p1), _ptr(p1t), _ptr(fws), nf, _stream()))
             factors = None if p1 is None else CondFactors(p1, p1_ld, L_all, mel2ph, p_idx, cond_ct, p1t)
             spk = shard.text_state_region(rec, lay, "spk") if cfg.multi_speaker else None
@@ -1552,7 +1682,7 @@ def frame_side_from_records(model: CMTotalTTS, groups, L_all, n_steps=4, seed=0,
             sample_groups.append((cond_ct, spk, noise, [int(t) for t in planned], factors))
             lens.append(torch.tensor([int(t) for t in planned], dtype=torch.int64, device=dev))
             if details is not None:
-                details.append({"mel2ph": mel2ph, "p_idx": p_idx, "ids": list(ids)})
+                details.append({"mel2ph": mel2ph, "p_idx": p_idx, "cwt": cwt, "ids": list(ids)})
         mels = sample_ragged(model, sample_groups, n_steps, tail_frames)
     return list(zip(mels, lens))
 
@@ -1565,17 +1695,23 @@ def synthesize_sharded(model: CMTotalTTS, texts, src_lens, spker_embeds=None, sp
     the mels of every rank all-gathered once.  An utterance longer than the largest bucket is truncated to it and reported.
     Noise is drawn per utterance from (seed, global index) (utterance_noise): results do not depend on the world size.
     Returns {"mels": [mel [len_i, 80]] in input order (every rank), "mel_len": the predicted lengths, "truncated": indices,
-    "plan": the plan; with `vocoder`: "wavs": [int16 [len_i * 256]] (shard.allgather_pcm per bucket)}."""
+    "plan": the plan; with `vocoder`: "wavs": [int16 [len_i * 256]] (shard.allgather_pcm per bucket)}.
+    d_control / p_control / e_control: numbers, or float32 tensors [B] (per utterance) / [B, L] (per phoneme, L = texts.shape[1])
+    indexed by GLOBAL utterance: every rank passes the same tables, each takes the rows of its own utterances for the text
+    side, and the pitch rows travel inside the text-state records to the rank that runs the utterance's frame side."""
     from . import shard
     if buckets is None:
         buckets = shard.FRAME_BUCKETS
-    model._require()
-    _note_process_group(model.lib)
     texts = torch.as_tensor(texts)
     src_lens = torch.as_tensor(src_lens)
     L_all = int(src_lens.max())                       # the reference's batch padding: the longest utterance of the batch
-    texts = texts[:, :L_all]
     n_items = int(texts.shape[0])
+    (p_control, e_control, d_control), tabs = _resolve_controls(n_items, int(texts.shape[1]), p_control, e_control, d_control)
+    tabs = {k: t[:, :L_all].contiguous() for k, t in tabs.items()}      # the tables are as wide as `texts` and cut with it
+    texts = texts[:, :L_all]
+    d_arg, e_arg, p_arg = tabs.get("d", d_control), tabs.get("e", 1.0), tabs.get("p", 1.0)
+    model._require()
+    _note_process_group(model.lib)
     vc = None
     if p_control != 1.0 or e_control != 1.0:
         vc = _lib.VarianceControlsStruct(p_control=float(p_control), e_control=float(e_control))
@@ -1583,8 +1719,8 @@ def synthesize_sharded(model: CMTotalTTS, texts, src_lens, spker_embeds=None, sp
     try:
         res = shard.two_phase(
             n_items,
-            lambda lo, hi: text_state_records(model, texts, src_lens, lo, hi, spker_embeds, speakers, d_control),
-            lambda groups: frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames),
+            lambda lo, hi: text_state_records(model, texts, src_lens, lo, hi, spker_embeds, speakers, d_arg, e_arg, p_arg),
+            lambda groups: frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, p_control=p_arg),
             group=group, buckets=buckets)
         if vocoder is not None:
             wavs = [None] * n_items

@@ -225,18 +225,20 @@ def allgather_buckets(mels, group=None, force: bool = False):
 # the data path's one all-gather of mels.
 
 TEXT_STATE_LAYOUT = 0x54530001
+TEXT_STATE_LAYOUT_P = 0x54530002          # revision 2: + the pitch control table's row ("pctl"), only with such a table installed
 TEXT_STATE_HEADER_BYTES = 64
 TEXT_STATE_REGIONS = ("out1", "h128", "spk", "cum")
 
 
-def text_state_layout(hidden: int, cwt_hidden: int, L_all: int):
+def text_state_layout(hidden: int, cwt_hidden: int, L_all: int, with_p: bool = False):
     """Byte layout of one text-state record (include/cmtts_hip.h, cmtts_text_state_*): {region: (offset, bytes)} and
     "record_bytes".  out1 fp32 [hidden][Lp], h128 fp32 [cwt_hidden][Lp], spk fp32 [hidden], cum int32 [L_all] (Lp = L_all rounded
-    up to 4), each 16-byte aligned behind the 64-byte header."""
+    up to 4), each 16-byte aligned behind the 64-byte header.  with_p: the record of a model with a pitch control table installed
+    (cmtts_set_control_tables, layout revision 2): a fifth region "pctl" fp32 [L_all], the utterance's row of the table."""
     Lp = (L_all + 3) // 4 * 4
-    sizes = {"out1": hidden * Lp * 4, "h128": cwt_hidden * Lp * 4, "spk": hidden * 4, "cum": L_all * 4}
+    sizes = {"out1": hidden * Lp * 4, "h128": cwt_hidden * Lp * 4, "spk": hidden * 4, "cum": L_all * 4, "pctl": L_all * 4}
     out, off = {}, TEXT_STATE_HEADER_BYTES
-    for r in TEXT_STATE_REGIONS:
+    for r in TEXT_STATE_REGIONS + (("pctl",) if with_p else ()):
         out[r] = (off, sizes[r])
         off += (sizes[r] + 15) // 16 * 16
     out["record_bytes"] = off

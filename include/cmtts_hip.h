@@ -63,7 +63,9 @@ const char* cmtts_version(void);
  * 6 — entry points only: the text-state records (cmtts_text_state_*) and cmtts_exchange_records of a sharded synthesis;
  * 7 — entry points only: windowed vocoding for streamed PCM (cmtts_vocoder_halo_frames, cmtts_vocoder_windows_workspace_bytes,
  * cmtts_vocoder_forward_windows);
- * 8 — options only: cmtts_model_set_option / cmtts_vocoder_set_option "batch_invariant" (a host detects support here).
+ * 8 — options only: cmtts_model_set_option / cmtts_vocoder_set_option "batch_invariant" (a host detects support here);
+ * still 8 — cmtts_set_control_tables (per-phoneme control tables) is a new entry point and a new struct: no existing layout or
+ * signature changes, so the number stays; a host detects it by looking the symbol up (dlsym).
  * A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
  * against before it passes a struct (cmtts_amd/_lib.py does at load time). */
 #define CMTTS_ABI_VERSION 8
@@ -127,6 +129,33 @@ typedef struct cmtts_variance_controls {
 } cmtts_variance_controls;
 int cmtts_set_variance_controls(cmtts_model* m, const cmtts_variance_controls* vc);
 
+/* ---- Per-utterance and per-phoneme controls: the three multiplications of the reference (model/modules.py:270 pitch, :326 energy,
+ * :369 duration) are elementwise, so a TABLE of factors in place of the scalar is the same model.  d, e, p: fp32 [B, ld] DEVICE
+ * pointers, one factor per phoneme (a per-utterance control = one value repeated along its row), valid while the forward calls run;
+ * each may be NULL on its own.  ld = the row pitch = the L (L_all) of the next text-side call; another L is CMTTS_E_INVALID there.
+ *   d: d_rounded[b,l] = max(rint(exp(log_d[b,l]) - 1) * d[b,l], 0); its integer part feeds the cumulative sums and mel_len as before
+ *   e: e_pred[b,l] = prediction * e[b,l], bucketized and returned (like e_control != 1)
+ *   p: cwt_out[b,t,:] *= p[b, mel2ph[b,t] - 1] for the frames of the utterance (all columns, the uv logit included, like p_control).
+ *      A padding frame (t >= mel_len[b]) takes the factor of the utterance's LAST frame: the f0 normalisation that follows takes its
+ *      mean and deviation over all T padded frames (utils/pitch_tools.py cwt2f0_norm), so the scale of the padding rows reaches every
+ *      valid frame, and the scalar p_control scales them too — with this rule a per-utterance factor gives, bit for bit, what the
+ *      utterance gets from the scalar in a batch of the same shape.  cmtts_text_forward(_ragged) copies p into the text workspace, cmtts_frame_forward* reads it
+ *      there: with p installed a text-state record carries the utterance's row as a fifth region (fp32 [L_all], layout word
+ *      0x54530002; cmtts_text_state_record_bytes grows accordingly) and cmtts_text_state_unpack restores it, so every rank of a
+ *      sharded synthesis must have the same "p installed" state — a frame-side rank needs p != NULL and ld, not the values.
+ * A table REPLACES the scalar of its control: a table together with d_control / e_control / p_control != 1 is CMTTS_E_INVALID at the
+ * forward call.  Teacher-forced targets keep their precedence (d_target over d, e_target over e; p scales the returned cwt_out
+ * also when a pitch target supplies the index, like p_control).  The caller's contract, as for all device data: p > 0 (it scales
+ * the uv logit), d >= 0, no NaN; entries at l >= src_lens[b] are ignored.  Without a table every path runs the scalar code.
+ * The tables stay on the model until replaced; NULL clears them. */
+typedef struct cmtts_control_tables {
+    const float* d;
+    const float* e;
+    const float* p;
+    int ld;
+} cmtts_control_tables;
+int cmtts_set_control_tables(cmtts_model* m, const cmtts_control_tables* t);
+
 /* ---- frame-level half (model/modules.py:373-412; LengthRegulator :415-448; dur_to_mel2ph
  * utils/tools.py:768-798; get_pitch_embedding cwt branch :259-317).  T = padded frame count chosen
  * by the host (max(mel_len) like the reference, or a static bucket).
@@ -163,7 +192,8 @@ int cmtts_frame_forward_sub_t(cmtts_model* m, const void* text_ws, int B_all, in
  * synthesize.py:195-227).  A record holds, for one utterance of a text workspace filled for L_all phonemes, what
  * cmtts_frame_forward_sub reads: out1 fp32 [hidden][Lp], h128 fp32 [cwt_hidden][Lp], spk fp32 [hidden] (the speaker vector,
  * = the speaker_emb output of the text side for multi-speaker models), cum int32 [L_all] (cumulative rounded durations: d_rounded =
- * its differences), behind a 64-byte header { int64 global index, int64 mel_len, int32 src_len, uint32 layout = 0x54530001,
+ * its differences) — and, only while a pitch control table is installed (cmtts_set_control_tables), its row fp32 [L_all] with layout
+ * 0x54530002 —, behind a 64-byte header { int64 global index, int64 mel_len, int32 src_len, uint32 layout = 0x54530001,
  * int32 L_all, hidden, cwt_hidden, n_regions, 24 bytes zero }; every region starts 16-byte aligned.  The size depends on
  * (config, L_all) only.  Records are plain bytes: any transport may move them between ranks of the same build.
  *   pack: rows int32 [n] (device) = the workspace rows to gather, in record order; global_idx int64 [n] (device, NULL = the row) and
