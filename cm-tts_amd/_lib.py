@@ -41,6 +41,11 @@ class SampleGroupStruct(C.Structure):
                 ("cond_p1", C.c_void_p), ("p1_ld", C.c_int32), ("L", C.c_int32), ("mel2ph", C.c_void_p), ("p_idx", C.c_void_p)]
 
 
+class NoiseGroupStruct(C.Structure):
+    """struct cmtts_noise_group (include/cmtts_hip.h)."""
+    _fields_ = [("seeds", C.c_void_p), ("B", C.c_int32), ("T", C.c_int32), ("out", C.c_void_p)]
+
+
 _vp, _i, _f, _sz, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 
 # name -> (restype, argtypes); must list every symbol include/cmtts_hip.h declares
@@ -71,6 +76,10 @@ SIGNATURES = {
     "cmtts_sample": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _sz, _vp]),
     "cmtts_sample_factored": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _sz, _vp, _vp, _i, _i, _vp, _vp]),
     "cmtts_sample_factored_t": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _sz, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "cmtts_noise_fill": (_i, [_vp, _i, _i, _i, _i, _i, _i64, _vp, _vp]),
+    "cmtts_noise_fill_groups": (_i, [C.POINTER(NoiseGroupStruct), _i, _i, _i, _i, _vp]),
+    "cmtts_sample_seeded_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "cmtts_sample_seeded": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _sz, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "cmtts_sample_ragged": (_i, [_vp, C.POINTER(SampleGroupStruct), _i, _i, C.POINTER(_f), C.POINTER(_f), _i, _vp]),
     "cmtts_vocoder_create": (_i, [C.POINTER(_vp)]),
     "cmtts_vocoder_set_tensor": (_i, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i]),
@@ -255,6 +264,20 @@ def internal_set(name, value):
         _internal = C.CDLL(LIB_PATH).cmtts_internal_set
         _internal.restype, _internal.argtypes = _i, [C.c_char_p, _i]
     return _internal(name if isinstance(name, bytes) else name.encode(), int(value))
+
+
+_noise_bits = None
+
+
+def internal_noise_bits(seeds, B, T, M, first_draw, n_draws, t0, bits, stream):
+    """csrc/internal_hooks.h: cmtts_internal_noise_bits — the raw Philox blocks of the seeded noise (tests only; pointers as
+    integers or c_void_p).  Returns the status."""
+    global _noise_bits
+    load()
+    if _noise_bits is None:
+        _noise_bits = C.CDLL(LIB_PATH).cmtts_internal_noise_bits
+        _noise_bits.restype, _noise_bits.argtypes = _i, [_vp, _i, _i, _i, _i, _i, _i64, _vp, _vp]
+    return _noise_bits(seeds, int(B), int(T), int(M), int(first_draw), int(n_draws), int(t0), bits, stream)
 
 
 def backend():

@@ -25,6 +25,7 @@
 #include "attention.h"
 #include "text_state.h"
 #include "stream_windows.h"
+#include "noise_philox.h"
 
 namespace {
 
@@ -2253,8 +2254,12 @@ int cmtts_schedule(const cmtts_model* m, int n_steps, float* sigmas, float* reno
 namespace {
 // The sampler on one padded (B, T) batch whose workspace is already carved.  noise_stride = elements between consecutive noise tensors
 // (B * T * n_mels for a whole batch; a sub-batch [b0, b0 + B) of a larger batch keeps the larger batch's stride).
+// seeds (cmtts_sample_seeded): device int64 [B] — x_T is generated straight into w.xcur (noise_philox.hip, draw 0 scaled by sigma_max:
+// the bits of a draw-0 tensor through k_scale) and `noise` is a buffer of n_steps tensors that takes the re-noise draws 1.. in one
+// launch on the side stream, beside the conditioner branch.
 int sample_core(cmtts_model* m, const DenWs& w, const float* noise, long noise_stride, const float* cond_ct, const float* speaker_emb, int B,
-                int T, int n_steps, const float* sigmas, const float* renoise_std, float* mel, hipStream_t s, const CondFactors* cf = nullptr) {
+                int T, int n_steps, const float* sigmas, const float* renoise_std, float* mel, hipStream_t s, const CondFactors* cf = nullptr,
+                const int64_t* seeds = nullptr) {
     const cmtts_config& c = m->cfg;
     const long nel = (long)B * T * c.n_mels;
     // once for all n_steps evaluations, on the side stream: joined before the first residual layer of the first evaluation
@@ -2281,7 +2286,17 @@ int sample_core(cmtts_model* m, const DenWs& w, const float* noise, long noise_s
             } else CHK(cond_factored(m, w, *cf, B, T, ss ? ss->side : s));
         } else CHK(cond_projections(m, w, cond_ct, B, T, ss ? ss->side : s));
     }
-    k_scale(noise, w.xcur, nel, c.sigma_max, s);        // x_T = randn * sigma_max (karras_diffusion.py:534)
+    const float* renoise0 = noise + noise_stride;       // draw 1 + i at renoise0 + i * noise_stride
+    if (seeds) {
+        renoise0 = noise;
+        int n_re = 0;
+        for (int i = 0; i < n_steps; ++i)
+            if (renoise_std[i] >= 0.0f) n_re = i + 1;
+        if (cmtts_launch_noise_fill(seeds, B, T, c.n_mels, 0, 1, 0, c.sigma_max, w.xcur, nullptr, (void*)s) != 0 ||
+            (n_re && cmtts_launch_noise_fill(seeds, B, T, c.n_mels, 1, n_re, 0, 1.0f, const_cast<float*>(noise), nullptr, (void*)(ss ? ss->side : s)) != 0))
+            return fail(CMTTS_E_HIP, "seeded noise launch failed");
+    } else
+        k_scale(noise, w.xcur, nel, c.sigma_max, s);        // x_T = randn * sigma_max (karras_diffusion.py:534)
     const float smin = c.sigma_min, sd2 = c.sigma_data * c.sigma_data;
     for (int i = 0; i < n_steps; ++i) {
         // get_scalings_for_boundary_condition in fp32 (karras_diffusion.py:87-102)
@@ -2300,7 +2315,7 @@ int sample_core(cmtts_model* m, const DenWs& w, const float* noise, long noise_s
         if (embed_side) CHK(step_embedding(m, w, w.tbuf, speaker_emb, B, ss->side, t_resc));
         const bool last = i + 1 == n_steps;
         const bool renoise = renoise_std[i] >= 0.0f;
-        const MelPost post = {w.xcur, renoise ? noise + (long)(1 + i) * noise_stride : nullptr, c_out, c_skip,
+        const MelPost post = {w.xcur, renoise ? renoise0 + (long)i * noise_stride : nullptr, c_out, c_skip,
                               renoise ? renoise_std[i] : 0.0f, last ? mel : w.xcur};
         CHK(denoiser_core(m, w, w.xcur, c_in, w.tbuf, cond_ct, speaker_emb, B, T, post, s, new_sigma && !embed_side, i == 0 ? ss : nullptr, t_resc, cfk, &cp_ready));
     }
@@ -2360,6 +2375,65 @@ int cmtts_sample_factored_t(cmtts_model* m, const float* noise, const float* con
     cf.p1t = cond_p1 ? cond_p1t : nullptr;      // the caller's channel-contiguous copy (cmtts_frame_forward_sub_t): no transpose at the sampler's entry
     return sample_core(m, w, noise, (long)B * T * c.n_mels, cond_ct, speaker_emb, B, T, n_steps, sigmas, renoise_std, mel, (hipStream_t)stream,
                        cond_p1 ? &cf : nullptr);
+}
+
+// ---- seeded per-utterance noise (noise_philox.hip)
+int cmtts_noise_fill(const int64_t* seeds, int B, int T, int M, int first_draw, int n_draws, int64_t t0, float* out, void* stream) {
+    if (!seeds || !out || B < 1 || T < 1 || M < 1 || n_draws < 1 || first_draw < 0 || t0 < 0)
+        return fail(CMTTS_E_INVALID, "cmtts_noise_fill: bad argument");
+    const int rc = cmtts_launch_noise_fill(seeds, B, T, M, first_draw, n_draws, t0, 1.0f, out, nullptr, stream);
+    if (rc == -2) return fail(CMTTS_E_UNSUPPORTED, "cmtts_noise_fill: B or n_draws > 65535, or T * ceil(M / 4) >= 2^31");
+    if (rc != 0) return fail(CMTTS_E_HIP, "cmtts_noise_fill: launch failed");
+    return 0;
+}
+
+int cmtts_noise_fill_groups(const cmtts_noise_group* groups, int n_groups, int M, int first_draw, int n_draws, void* stream) {
+    if (!groups || n_groups < 1 || M < 1 || n_draws < 1 || first_draw < 0) return fail(CMTTS_E_INVALID, "cmtts_noise_fill_groups: bad argument");
+    std::vector<NoiseGroup> gs((size_t)n_groups);
+    for (int g = 0; g < n_groups; ++g) {
+        const cmtts_noise_group& G = groups[g];
+        if (!G.seeds || !G.out || G.B < 1 || G.T < 1) return fail(CMTTS_E_INVALID, "cmtts_noise_fill_groups: bad group");
+        gs[g] = NoiseGroup{G.seeds, G.out, G.B, G.T, 0, 1};
+    }
+    const int rc = cmtts_launch_noise_fill_groups(gs.data(), n_groups, M, first_draw, n_draws, stream);
+    if (rc == -2) return fail(CMTTS_E_UNSUPPORTED, "cmtts_noise_fill_groups: n_draws > 65535 or a launch of more than 2^31 - 1 workgroups");
+    if (rc != 0) return fail(CMTTS_E_HIP, "cmtts_noise_fill_groups: launch failed");
+    return 0;
+}
+
+int cmtts_internal_noise_bits(const int64_t* seeds, int B, int T, int M, int first_draw, int n_draws, int64_t t0, uint32_t* bits, void* stream) {
+    if (!seeds || !bits || B < 1 || T < 1 || M < 1 || n_draws < 1 || first_draw < 0 || t0 < 0)
+        return fail(CMTTS_E_INVALID, "cmtts_internal_noise_bits: bad argument");
+    if (cmtts_launch_noise_fill(seeds, B, T, M, first_draw, n_draws, t0, 1.0f, nullptr, bits, stream) != 0)
+        return fail(CMTTS_E_HIP, "cmtts_internal_noise_bits: launch failed");
+    return 0;
+}
+
+// The denoiser workspace, then the re-noise draws 1 .. n_steps of the batch ([n_steps][B][1][T][n_mels], 256-byte aligned).
+static size_t seeded_tail_offset(const cmtts_config& c, int B, int T) { return (carve_den(c, B, T, nullptr).bytes + 255) & ~(size_t)255; }
+size_t cmtts_sample_seeded_workspace_bytes(const cmtts_model* m, int B, int T, int n_steps) {
+    if (!m || B < 1 || T < 1 || n_steps < 1) return 0;
+    return seeded_tail_offset(m->cfg, B, T) + (size_t)n_steps * B * T * m->cfg.n_mels * sizeof(float);
+}
+
+int cmtts_sample_seeded(cmtts_model* m, const int64_t* seeds, const float* cond_ct, const float* speaker_emb, int B, int T,
+                        int n_steps, const float* sigmas, const float* renoise_std, float* mel, void* ws, size_t ws_bytes,
+                        void* stream, const float* cond_p1, const float* cond_p1t, int p1_ld, int L, const int64_t* mel2ph, const int64_t* p_idx) {
+    if (!m || !m->finalized) return fail(CMTTS_E_INVALID, "model not finalized");
+    if (!seeds || !cond_ct || !mel || !ws || !sigmas || !renoise_std || B <= 0 || T <= 0 || n_steps < 1)
+        return fail(CMTTS_E_INVALID, "cmtts_sample_seeded: bad argument");
+    if (cond_p1 && (!mel2ph || !p_idx || L <= 0 || p1_ld < L)) return fail(CMTTS_E_INVALID, "cmtts_sample_seeded: incomplete factors");
+    CHK(check_batch_invariant(m));
+    const cmtts_config& c = m->cfg;
+    if (B > 65535) return fail(CMTTS_E_UNSUPPORTED, "cmtts_sample_seeded: B > 65535");
+    DenWs w = carve_den(c, B, T, ws);
+    if (ws_bytes < cmtts_sample_seeded_workspace_bytes(m, B, T, n_steps)) return fail(CMTTS_E_WORKSPACE, "seeded sampler workspace too small");
+    const float* tail = reinterpret_cast<const float*>(static_cast<char*>(ws) + seeded_tail_offset(c, B, T));
+    CondFactors cf;
+    cf.p1 = cond_p1; cf.ldp = p1_ld; cf.L = L; cf.mel2ph = mel2ph; cf.p_idx = p_idx;
+    cf.p1t = cond_p1 ? cond_p1t : nullptr;
+    return sample_core(m, w, tail, (long)B * T * c.n_mels, cond_ct, speaker_emb, B, T, n_steps, sigmas, renoise_std, mel, (hipStream_t)stream,
+                       cond_p1 ? &cf : nullptr, seeds);
 }
 
 // karras_sample_tts for a RAGGED shard (BASELINE.json configs[3]: utterances dealt into static frame buckets): every group is a

@@ -34,6 +34,9 @@ int cmtts_internal_cond_factored(struct cmtts_model* m, const float* p1, int p1_
 // Test hook: the streaming rounds' mel window gather alone (stream_windows.hip: mel_window_gather_kernel).  mel_ct [B][80][T] ->
 // out [N][80][Tw], windows: device [N][4] int32 (utterance, start, core_off, core_len) — NOT validated here (the caller's test does).
 int cmtts_internal_mel_window_gather(const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, float* out, void* stream);
+// Test hook: the raw Philox4x32-10 blocks of the seeded noise (noise_philox.hip), before Box-Muller: bits uint32
+// [n_draws][B][T][ceil(M / 4)][4] for the arguments of cmtts_noise_fill (seeds: device int64 [B]).
+int cmtts_internal_noise_bits(const int64_t* seeds, int B, int T, int M, int first_draw, int n_draws, int64_t t0, uint32_t* bits, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import noise as _noise
 from .config import CMTTSConfig, HifiGanConfig
 
 
@@ -530,6 +531,119 @@ class DummyGenerator:
         return torch.randn_like(*args, **kwargs)
 
 
+def _device_seeds(seeds, B, device):
+    """`seeds` as int64 [B] on `device`: a tensor / array / sequence of B utterance seeds as it is, ONE int expanded with
+    noise.utterance_seeds(int, arange(B))."""
+    if isinstance(seeds, (int, np.integer)):
+        seeds = _noise.utterance_seeds(int(seeds), np.arange(int(B)))
+    if not isinstance(seeds, torch.Tensor):
+        seeds = torch.from_numpy(np.ascontiguousarray(_noise._as_u64(seeds).view(np.int64)))
+    if seeds.dtype != torch.int64 or tuple(seeds.shape) != (int(B),):
+        raise ValueError(f"seeds: expected int64 [{int(B)}], got {seeds.dtype} {tuple(seeds.shape)}")
+    return seeds.to(device=device).contiguous()
+
+
+def seeded_noise(seeds, n_noise, T, n_mels=80, device="cuda:0", first_draw=0, t0=0):
+    """The sampler's noise fp32 [n_noise, B, 1, T, n_mels] of the utterances with the int64 seeds [B] (cmtts_noise_fill, one
+    launch): draws first_draw .. first_draw + n_noise - 1, frames t0 .. t0 + T - 1.  The value at (seed, draw, frame, mel bin) is
+    a pure function of those four numbers (noise.py states it in numpy): a row does not depend on B, on its position or on T."""
+    lib = _lib.load()
+    dev = _norm_device(device)
+    B = int(seeds.shape[0]) if hasattr(seeds, "shape") else len(seeds)
+    sd = _device_seeds(seeds, B, dev)
+    with torch.cuda.device(dev):
+        out = torch.empty(int(n_noise), B, 1, int(T), int(n_mels), dtype=torch.float32, device=dev)
+        _lib.check(lib.cmtts_noise_fill(_ptr(sd), B, int(T), int(n_mels), int(first_draw), int(n_noise), int(t0), _ptr(out), _stream()))
+    return out
+
+
+def seeded_noise_groups(groups, n_noise, n_mels=80, device="cuda:0", first_draw=0):
+    """seeded_noise for every padded group of a ragged shard in one launch (cmtts_noise_fill_groups).
+    groups: [(seeds int64 [B_g], T_g)] -> [noise [n_noise, B_g, 1, T_g, n_mels]]."""
+    lib = _lib.load()
+    dev = _norm_device(device)
+    arr = (_lib.NoiseGroupStruct * len(groups))()
+    outs, keep = [], []
+    with torch.cuda.device(dev):
+        for g, (seeds, T) in zip(arr, groups):
+            B = int(seeds.shape[0]) if hasattr(seeds, "shape") else len(seeds)
+            sd = _device_seeds(seeds, B, dev)
+            out = torch.empty(int(n_noise), B, 1, int(T), int(n_mels), dtype=torch.float32, device=dev)
+            g.seeds, g.B, g.T, g.out = sd.data_ptr(), B, int(T), out.data_ptr()
+            keep.append(sd)
+            outs.append(out)
+        if outs:
+            _lib.check(lib.cmtts_noise_fill_groups(arr, len(outs), int(n_mels), int(first_draw), int(n_noise), _stream()))
+    return outs
+
+
+class IndivGenerator:
+    """model/cm_tool/random_util.py:97-182 ("determ-indiv"): noise that does not depend on the batch size or on the number of
+    ranks — sample i of the run has its own stream, whichever batch and rank draws it.  Here sample i's stream is the seeded noise
+    of noise.utterance_seeds(seed, [i]) and the k-th randn / randn_like call since set_done_samples is draw k of it (draw 0 is x_T,
+    draw 1 + i the re-noise after evaluation i), generated on the device by cmtts_noise_fill.
+    A tensor with first dimension n takes the samples done_samples + rank + k * world for k < n, clamped to num_samples - 1.
+    Shapes: [n, 1, T, n_mels] or [n, T, n_mels] (the sampler's)."""
+
+    def __init__(self, num_samples, seed=0, rank=None, world=None):
+        if rank is None or world is None:
+            import torch.distributed as dist
+            on = dist.is_available() and dist.is_initialized()
+            rank = (dist.get_rank() if on else 0) if rank is None else rank
+            world = (dist.get_world_size() if on else 1) if world is None else world
+        self.num_samples, self.seed, self.rank, self.world_size = int(num_samples), int(seed), int(rank), int(world)
+        self.done_samples = 0
+        self.draw = 0
+
+    def get_size_and_indices(self, size):
+        """random_util.py:119-129: (the size of one sample's tensor, the global sample index of every row)."""
+        return (1, *size[1:]), _noise.indiv_indices(size[0], self.num_samples, self.done_samples, self.rank, self.world_size)
+
+    def seeds_for(self, n):
+        """int64 numpy [n]: the utterance seeds of the next n rows."""
+        return _noise.utterance_seeds(self.seed, _noise.indiv_indices(n, self.num_samples, self.done_samples, self.rank, self.world_size))
+
+    def randn(self, *size, dtype=torch.float, device="cpu"):
+        if len(size) == 1 and isinstance(size[0], (tuple, list, torch.Size)):
+            size = tuple(size[0])
+        if dtype not in (torch.float, torch.float32):
+            raise NotImplementedError("determ-indiv: float32 noise only")
+        if len(size) < 3 or any(int(v) != 1 for v in size[1:-2]):
+            raise NotImplementedError(f"determ-indiv: shape {tuple(size)}; the seeded noise is defined on [n, 1, T, n_mels] / [n, T, n_mels]")
+        if _norm_device(device).type != "cuda":
+            raise NotImplementedError("determ-indiv: the noise is generated on the GPU (cmtts_noise_fill); pass device=")
+        z = seeded_noise(self.seeds_for(size[0]), 1, size[-2], size[-1], device, first_draw=self.draw)
+        self.draw += 1
+        return z.reshape(tuple(int(v) for v in size))
+
+    def randn_like(self, tensor):
+        return self.randn(*tensor.shape, dtype=tensor.dtype, device=tensor.device)
+
+    def set_done_samples(self, done_samples):
+        self.done_samples = int(done_samples)
+        self.draw = 0
+
+    def get_seed(self):
+        return self.seed
+
+    def set_seed(self, seed):
+        self.seed = int(seed)
+        self.draw = 0
+
+
+def get_generator(generator, num_samples=0, seed=0):
+    """model/cm_tool/random_util.py:6-14."""
+    if generator == "dummy":
+        return DummyGenerator()
+    if generator == "determ-indiv":
+        return IndivGenerator(num_samples, seed)
+    if generator == "determ":
+        raise NotImplementedError('generator "determ" draws num_samples full tensors from one stream and keeps this rank\'s rows of them '
+                                  '(random_util.py:28-94): its cost grows with the run, not with the batch.  "determ-indiv" gives '
+                                  "the same independence from batch size and world size per sample")
+    raise NotImplementedError(generator)
+
+
 def check_async_error():
     """Raise if a persistent denoiser launch that has completed reported a neighbour-wait timeout (cmtts_poll_error)."""
     _lib.check(_lib.load().cmtts_poll_error())
@@ -542,15 +656,22 @@ def synchronize(device=None):
     check_async_error()
 
 
-def sample_with_cond(model: CMTotalTTS, cond_ct, speaker_emb, n_steps, noise, factors=None):
+def sample_with_cond(model: CMTotalTTS, cond_ct, speaker_emb, n_steps, noise=None, factors=None, seeds=None):
     """T-step consistency sampling on precomputed conditioning (cmtts_sample).
     noise: fp32 [n_noise,B,1,T,80] on device.  factors: the duration net's out["cond_factors"] for THIS cond_ct (default: the ones the
     duration net attached to the tensor object it returned; the conditioner projections are then expanded from them,
-    cmtts_sample_factored — an unmodified, same-storage cond_ct only, else the dense GEMM).  Returns mel [B,T,80]."""
+    cmtts_sample_factored — an unmodified, same-storage cond_ct only, else the dense GEMM).  Returns mel [B,T,80].
+    seeds (in place of noise): int64 [B] utterance seeds, or one int (noise.utterance_seeds(int, arange(B))) — the sampler
+    generates the seeded noise itself (cmtts_sample_seeded: no noise tensor for x_T, one launch for the re-noise draws); the mel
+    has the bits of noise=seeded_noise(seeds, n_noise, T)."""
     model._require()
     lib, dev, cfg = model.lib, model.device, model.config
     B, H, T = cond_ct.shape
     n_noise = 1 if n_steps == 1 else n_steps + 1
+    if (noise is None) == (seeds is None):
+        raise ValueError("sample_with_cond: give noise or seeds (one of them)")
+    if seeds is not None:
+        return _sample_seeded(model, cond_ct, speaker_emb, n_steps, _device_seeds(seeds, B, dev), factors)
     assert noise.shape[0] >= n_noise and tuple(noise.shape[1:]) == (B, 1, T, cfg.n_mels)
     sig = (C.c_float * n_steps)()
     std = (C.c_float * n_steps)()
@@ -569,6 +690,36 @@ def sample_with_cond(model: CMTotalTTS, cond_ct, speaker_emb, n_steps, noise, fa
             _lib.check(lib.cmtts_sample(model._h, _ptr(noise), _ptr(cond_ct), _ptr(speaker_emb), B, T, n_steps, sig, std,
                                         _ptr(mel), _ptr(ws), nb, _stream()))
     return mel
+
+
+def _sample_seeded(model, cond_ct, speaker_emb, n_steps, seeds, factors):
+    lib, dev, cfg = model.lib, model.device, model.config
+    B, H, T = cond_ct.shape
+    sig = (C.c_float * n_steps)()
+    std = (C.c_float * n_steps)()
+    _lib.check(lib.cmtts_schedule(model._h, n_steps, sig, std))
+    with torch.cuda.device(dev):
+        mel = torch.empty(B, T, cfg.n_mels, dtype=torch.float32, device=dev)
+        nb = lib.cmtts_sample_seeded_workspace_bytes(model._h, B, T, n_steps)
+        ws = model._ws.get("den_seeded", nb, dev)
+        if factors is None:
+            factors = getattr(cond_ct, "_cmtts_factors", None)
+        f = factors if factors is not None and factors.matches(cond_ct) else None
+        _lib.check(lib.cmtts_sample_seeded(model._h, _ptr(seeds), _ptr(cond_ct), _ptr(speaker_emb), B, T, n_steps, sig, std,
+                                           _ptr(mel), _ptr(ws), nb, _stream(), _ptr(f.p1 if f else None), _ptr(f.p1t if f else None),
+                                           f.p1_ld if f else 0, f.L if f else 0, _ptr(f.mel2ph if f else None), _ptr(f.p_idx if f else None)))
+    return mel
+
+
+def _draw_sampler_noise(gen, B, T, n_mels, draws, device):
+    """The sampler's noise from a generator: x0 = randn, then randn_like(x0) per further draw; an IndivGenerator gives the same
+    bits in one fill."""
+    if isinstance(gen, IndivGenerator):
+        noise = seeded_noise(gen.seeds_for(B), draws, T, n_mels, device, first_draw=gen.draw)
+        gen.draw += draws
+        return noise
+    x0 = gen.randn(B, 1, T, n_mels, device=device)
+    return torch.stack([x0] + [gen.randn_like(x0) for _ in range(draws - 1)], 0).float()
 
 
 def sample_ragged(model: CMTotalTTS, groups, n_steps, tail_frames=0):
@@ -1036,11 +1187,14 @@ def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_
 
 def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=None, speakers=None, n_steps=4, noise=None,
                       chunk_frames=STREAM_CHUNK_FRAMES, generator=None, max_wav_value=32768.0,
-                      p_control=1.0, e_control=1.0, d_control=1.0):
+                      p_control=1.0, e_control=1.0, d_control=1.0, seeds=None):
     """Text -> streamed PCM: the duration net and the T-step sampler exactly as CMTotalTTSSynthesize.synthesize runs them (noise
     [n_noise, B, 1, T, 80] drawn as x0 = randn, then randn_like(x0) per further step, unless given), then vocoder_infer_stream on
     the mels trimmed to their predicted lengths.  Yields (utterance, sample_offset, pcm int16 numpy, is_last).
-    p_control / e_control / d_control: numbers, [B] or [B, L] float32 tensors (DurationPitchSpeakerNet.forward)."""
+    p_control / e_control / d_control: numbers, [B] or [B, L] float32 tensors (DurationPitchSpeakerNet.forward).
+    seeds: int64 [B] utterance seeds or one int — seeded noise generated by the sampler (sample_with_cond), in place of noise / generator."""
+    if seeds is not None and noise is not None:
+        raise ValueError("synthesize_stream: give noise or seeds, not both")
     out = model.duration_pitch_energy_net(speakers=speakers, texts=texts, src_lens=src_lens, spker_embeds=spker_embeds,
                                           p_control=p_control, e_control=e_control, d_control=d_control)
     B, T, _ = out["cond"].shape
@@ -1048,11 +1202,9 @@ def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=
     if n_steps not in (1, 2, 4):
         raise ValueError("n_steps must be 1, 2 or 4 (synthesize.py:111-147)")
     draws = 1 if n_steps == 1 else n_steps + 1
-    if noise is None:
-        gen = generator or DummyGenerator()
-        x0 = gen.randn(B, 1, T, cfg.n_mels, device=model.device)
-        noise = torch.stack([x0] + [gen.randn_like(x0) for _ in range(draws - 1)], 0).float()
-    mel = sample_with_cond(model, out["cond_ct"], out["speaker_emb"], n_steps, noise, factors=out.get("cond_factors"))
+    if noise is None and seeds is None:
+        noise = _draw_sampler_noise(generator or DummyGenerator(), B, T, cfg.n_mels, draws, model.device)
+    mel = sample_with_cond(model, out["cond_ct"], out["speaker_emb"], n_steps, noise, factors=out.get("cond_factors"), seeds=seeds)
     mel_lens = out["mel_lens"].cpu().tolist()
     yield from vocoder_infer_stream(mel.transpose(1, 2), vocoder, mel_lens, chunk_frames, max_wav_value)
 
@@ -1482,10 +1634,12 @@ class CMTotalTTSSynthesize:
         model.eval()
         return model, diffusion
 
-    def synthesize(self, batch, p_control=None, e_control=None, d_control=None):
+    def synthesize(self, batch, p_control=None, e_control=None, d_control=None, seeds=None):
         """batch = (ids, raw_texts, speakers, texts, src_lens, max_src_len, spker_embeds) after to_device (:88-153).
         The controls given at construction apply (numbers, or float32 [B] / [B, L] tensors); a control given here replaces the
-        constructor's for this call — a table on top of a constructor scalar other than 1 is a ValueError."""
+        constructor's for this call — a table on top of a constructor scalar other than 1 is a ValueError.
+        seeds: int64 [B] utterance seeds or one int — the sampler generates the seeded noise itself (sample_with_cond) and the
+        generator is not drawn from.  A "determ-indiv" generator (get_generator) without `seeds` does the same with its own seeds."""
         kw = {"speakers": batch[2], "texts": batch[3], "src_lens": batch[4], "spker_embeds": batch[-1]}
         _check_no_scalar_with_table((self.p_control, self.e_control, self.d_control), p_control, e_control, d_control)
         for name, own, given in (("p_control", self.p_control, p_control), ("e_control", self.e_control, e_control),
@@ -1510,6 +1664,8 @@ class CMTotalTTSSynthesize:
             abs(float(cm.get("sigma_max", cfg.sigma_max)) - cfg.sigma_max) < 1e-6 * cfg.sigma_max and \
             abs(float(cm.get("sigma_min", cfg.sigma_min)) - cfg.sigma_min) < 1e-6 * cfg.sigma_min
         gen = self.generator or DummyGenerator()
+        if seeds is not None and not fusable:
+            raise NotImplementedError("seeds: the fused sampler only (a distilled model with the config's sigmas)")
         if not fusable:      # e.g. a progdist teacher: the reference's sampler loops, host-side (karras_sample_tts routes)
             sample = karras_sample_tts(self.diffusion, self.model, (B, 1, T, cfg.n_mels), steps=2, model_kwargs=kw,
                                        device=self.device, sigma_min=float(cm.get("sigma_min", cfg.sigma_min)),
@@ -1517,10 +1673,14 @@ class CMTotalTTSSynthesize:
                                        sampler="onestep" if steps == 1 else "multistep",
                                        ts=None if steps == 1 else (0,) * steps + (1,), generator=gen)
         else:                # the duration net ran once above; the reference's in-sampler re-runs are bit-identical
-            x0 = gen.randn(B, 1, T, cfg.n_mels, device=self.model.device)
-            noise = torch.stack([x0] + [gen.randn_like(x0) for _ in range(draws - 1)], 0).float()
+            noise = None
+            if seeds is None and isinstance(gen, IndivGenerator) and gen.draw == 0:
+                seeds = gen.seeds_for(B)          # the sampler makes draws 0 .. draws - 1 itself
+                gen.draw += draws
+            elif seeds is None:
+                noise = _draw_sampler_noise(gen, B, T, cfg.n_mels, draws, self.model.device)
             sample = sample_with_cond(self.model, out_dict["cond_ct"], out_dict["speaker_emb"], n_steps, noise,
-                                      factors=out_dict.get("cond_factors"))
+                                      factors=out_dict.get("cond_factors"), seeds=seeds)
         out_put = [None] * 12
         out_put[0] = sample
         out_put[10] = kw["src_lens"]
@@ -1626,14 +1786,16 @@ def text_state_records(model: CMTotalTTS, texts, src_lens, lo, hi, spker_embeds=
     return records, mel_len
 
 
-def frame_side_from_records(model: CMTotalTTS, groups, L_all, n_steps=4, seed=0, tail_frames=16, details=None, p_control=1.0):
+def frame_side_from_records(model: CMTotalTTS, groups, L_all, n_steps=4, seed=0, tail_frames=16, details=None, p_control=1.0, seeds=None):
     """groups: [(bucket, records uint8 [n, R], utterance ids [n], planned lengths [n])] (shard.two_phase).  Every group's records are
     unpacked into a text workspace of its own, its frame side runs with T = bucket, and ONE cmtts_sample_ragged call samples all
     groups (each utterance trimmed to its planned length + tail_frames) with utterance_noise(seed, id).  Returns [(mel [n, bucket, 80],
     mel_len int64 [n])]; `details` (a list) receives one {"mel2ph", "p_idx", "cwt", "ids"} per group.
     p_control: what the text side was given (a number, or a float32 tensor [B] / [B, L_all] over the whole batch).  A table's rows
     arrive in the records (layout revision 2); here it only says that they do — every rank must agree on that, record sizes depend
-    on it.  A number other than 1 is the caller's cmtts_set_variance_controls around both phases (synthesize_sharded)."""
+    on it.  A number other than 1 is the caller's cmtts_set_variance_controls around both phases (synthesize_sharded).
+    seeds: int64 numpy / CPU tensor indexed by GLOBAL utterance id — seeded noise (one cmtts_noise_fill_groups launch for all
+    groups) in place of utterance_noise(seed, id)."""
     from . import shard
     cfg, lib, dev = model.config, model.lib, model.device
     p_tab = None
@@ -1649,16 +1811,20 @@ def frame_side_from_records(model: CMTotalTTS, groups, L_all, n_steps=4, seed=0,
     use_p1 = getattr(model, "_precision_mode", 0) == 0 and model._cond_factors
     inst = _InstalledTables(model, p_tab or {}, L_all, present_only=("p",))
     try:
-        return _frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, details, lay, p1_ld, use_p1, n_noise)
+        return _frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, details, lay, p1_ld, use_p1, n_noise, seeds)
     finally:
         inst.clear()
 
 
-def _frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, details, lay, p1_ld, use_p1, n_noise):
+def _frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, details, lay, p1_ld, use_p1, n_noise, seeds=None):
     from . import shard
     cfg, lib, dev = model.config, model.lib, model.device
     sample_groups, lens = [], []
     with torch.cuda.device(dev):
+        seeded = None
+        if seeds is not None:
+            sv = seeds.cpu().numpy() if isinstance(seeds, torch.Tensor) else np.asarray(seeds)
+            seeded = seeded_noise_groups([(sv[[int(i) for i in ids]], int(bucket)) for bucket, _, ids, _ in groups], n_noise, cfg.n_mels, dev)
         f = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
         for k, (bucket, rec, ids, planned) in enumerate(groups):
             n, T = len(ids), int(bucket)
@@ -1678,7 +1844,7 @@ def _frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, d
                                                      _ptr(p_idx), None, _ptr(p1), _ptr(p1t), _ptr(fws), nf, _stream()))
             factors = None if p1 is None else CondFactors(p1, p1_ld, L_all, mel2ph, p_idx, cond_ct, p1t)
             spk = shard.text_state_region(rec, lay, "spk") if cfg.multi_speaker else None
-            noise = torch.stack([utterance_noise(seed, i, n_noise, T, cfg.n_mels, dev) for i in ids], 1)
+            noise = seeded[k] if seeded is not None else torch.stack([utterance_noise(seed, i, n_noise, T, cfg.n_mels, dev) for i in ids], 1)
             sample_groups.append((cond_ct, spk, noise, [int(t) for t in planned], factors))
             lens.append(torch.tensor([int(t) for t in planned], dtype=torch.int64, device=dev))
             if details is not None:
@@ -1688,12 +1854,15 @@ def _frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, d
 
 
 def synthesize_sharded(model: CMTotalTTS, texts, src_lens, spker_embeds=None, speakers=None, n_steps=4, group=None, seed=0,
-                       buckets=None, vocoder=None, d_control=1.0, p_control=1.0, e_control=1.0, tail_frames=16, max_wav_value=32768.0):
+                       buckets=None, vocoder=None, d_control=1.0, p_control=1.0, e_control=1.0, tail_frames=16, max_wav_value=32768.0,
+                       seeds=None):
     """A batch of texts (synthesize.py batch mode: texts int64 [B, L], src_lens [B], the same on every rank) over the ranks of
     `group` (torch.distributed; none initialised = one rank): text side of this rank's slice (shard.shard_range), lengths agreed,
     text-state records moved to the ranks of the agreed plan_shards(mel_len) (shard.two_phase), frame side and sampler per bucket,
     the mels of every rank all-gathered once.  An utterance longer than the largest bucket is truncated to it and reported.
     Noise is drawn per utterance from (seed, global index) (utterance_noise): results do not depend on the world size.
+    seeds: int64 [B] utterance seeds by GLOBAL utterance (the same on every rank), or one int (noise.utterance_seeds(int, arange(B))):
+    seeded noise instead (seeded_noise_groups, one launch per rank) — an utterance's noise then follows its seed, not its position.
     Returns {"mels": [mel [len_i, 80]] in input order (every rank), "mel_len": the predicted lengths, "truncated": indices,
     "plan": the plan; with `vocoder`: "wavs": [int16 [len_i * 256]] (shard.allgather_pcm per bucket)}.
     d_control / p_control / e_control: numbers, or float32 tensors [B] (per utterance) / [B, L] (per phoneme, L = texts.shape[1])
@@ -1706,6 +1875,8 @@ def synthesize_sharded(model: CMTotalTTS, texts, src_lens, spker_embeds=None, sp
     src_lens = torch.as_tensor(src_lens)
     L_all = int(src_lens.max())                       # the reference's batch padding: the longest utterance of the batch
     n_items = int(texts.shape[0])
+    if seeds is not None:
+        seeds = _device_seeds(seeds, n_items, "cpu").numpy()
     (p_control, e_control, d_control), tabs = _resolve_controls(n_items, int(texts.shape[1]), p_control, e_control, d_control)
     tabs = {k: t[:, :L_all].contiguous() for k, t in tabs.items()}      # the tables are as wide as `texts` and cut with it
     texts = texts[:, :L_all]
@@ -1720,7 +1891,7 @@ def synthesize_sharded(model: CMTotalTTS, texts, src_lens, spker_embeds=None, sp
         res = shard.two_phase(
             n_items,
             lambda lo, hi: text_state_records(model, texts, src_lens, lo, hi, spker_embeds, speakers, d_arg, e_arg, p_arg),
-            lambda groups: frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, p_control=p_arg),
+            lambda groups: frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, p_control=p_arg, seeds=seeds),
             group=group, buckets=buckets)
         if vocoder is not None:
             wavs = [None] * n_items

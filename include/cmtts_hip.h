@@ -247,6 +247,41 @@ int cmtts_sample_factored_t(cmtts_model* m, const float* noise, const float* con
                             float* mel, void* ws, size_t ws_bytes, void* stream,
                             const float* cond_p1, const float* cond_p1t, int p1_ld, int L, const int64_t* mel2ph, const int64_t* p_idx);
 
+/* ---- seeded per-utterance sampler noise, generated on the device (noise_philox.hip; the reference's "determ-indiv" generator,
+ * model/cm_tool/random_util.py:97-182, in its stronger form: one request — text, speaker, controls, seed — gives one result
+ * whatever it is batched with).  The value at (utterance seed, draw, frame, mel bin) is a pure function of those four numbers;
+ * B, the row, the padded T, the bucket, the rank and the launch shape do not enter.  The definition (cmtts_amd/noise.py states it in numpy):
+ *   bits     Philox4x32-10 with the standard constants (multipliers 0xD2511F53, 0xCD9E8D57; Weyl key increments 0x9E3779B9,
+ *            0xBB67AE85; ten rounds; per round c <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), then the key bump)
+ *   key      the utterance's 64-bit seed: (seed mod 2^32, seed >> 32)
+ *   counter  (j mod 2^32, j >> 32, draw, 0x434D5454), j = (t0 + t) * ceil(M / 4) + floor(m / 4): t the frame row of the tensor,
+ *            t0 the tensor's first frame, m the mel bin, M = n_mels; element (t, m) is lane m mod 4 of its block
+ *   normals  Box-Muller on 24-bit uniforms (every conversion exact in fp32): u1 = ((x_a >> 8) + 1) * 2^-24, u2 = (x_b >> 8) * 2^-24,
+ *            r = sqrt(-2 ln u1); lanes 0, 1 = r cos(2 pi u2), r sin(2 pi u2) from (x0, x1), lanes 2, 3 the same from (x2, x3); |z| <= 5.77
+ *   draws    the sampler's numbering: draw 0 is x_T, draw 1 + i the re-noise after evaluation i
+ *   math     logf, sqrtf, sincospif(2 u2) — full-precision device functions, no fast intrinsics, no fast-math flag
+ * How a request seed becomes utterance seeds is the host's business (cmtts_amd/noise.py: utterance_seeds, splitmix64).
+ * seeds: DEVICE int64 [B].  out: fp32 [n_draws,B,1,T,M], draws first_draw .. first_draw + n_draws - 1, frames t0 .. t0 + T - 1.
+ * One launch.  Null pointers, B / T / M / n_draws < 1, first_draw < 0, t0 < 0: CMTTS_E_INVALID before any launch. */
+int cmtts_noise_fill(const int64_t* seeds, int B, int T, int M, int first_draw, int n_draws, int64_t t0, float* out, void* stream);
+/* ... for every padded (B, T) group of a ragged shard in ONE launch (t0 = 0): `groups` is a HOST array, the table travels by
+ * value in the kernel arguments, 32 groups per launch (more groups = more launches). */
+typedef struct cmtts_noise_group {
+    const int64_t* seeds;        /* device [B] */
+    int32_t B, T;
+    float* out;                  /* device [n_draws,B,1,T,M] */
+} cmtts_noise_group;
+int cmtts_noise_fill_groups(const cmtts_noise_group* groups, int n_groups, int M, int first_draw, int n_draws, void* stream);
+/* cmtts_sample_factored_t without a noise argument: x_T = sigma_max * draw 0 is generated straight into the sampler's state and the
+ * re-noise draws into the tail of the workspace (one launch, beside the conditioner branch).  The mel has the bits of
+ * cmtts_sample_factored_t on the tensor cmtts_noise_fill(seeds, B, T, n_mels, 0, n_noise, 0, ...) writes.
+ * ws: cmtts_sample_seeded_workspace_bytes(m, B, T, n_steps) bytes (the denoiser workspace + n_steps noise tensors). */
+size_t cmtts_sample_seeded_workspace_bytes(const cmtts_model* m, int B, int T, int n_steps);
+int cmtts_sample_seeded(cmtts_model* m, const int64_t* seeds, const float* cond_ct, const float* speaker_emb,
+                        int B, int T, int n_steps, const float* sigmas_host, const float* renoise_std_host,
+                        float* mel, void* ws, size_t ws_bytes, void* stream,
+                        const float* cond_p1, const float* cond_p1t, int p1_ld, int L, const int64_t* mel2ph, const int64_t* p_idx);
+
 /* ---- the same sampler for a RAGGED shard (BASELINE.json configs[3]: variable-length utterances dealt into static frame buckets;
  * new work — the reference synthesizes one padded batch at a time, synthesize.py:195-227).  Every group is one padded (B, T) batch
  * with its own noise / conditioning / output / workspace (cmtts_denoiser_workspace_bytes(m, B, T)) exactly as cmtts_sample takes
