@@ -91,6 +91,11 @@ SIGNATURES = {
     "cmtts_vocoder_halo_frames": (_i, [_vp]),
     "cmtts_vocoder_windows_workspace_bytes": (_sz, [_vp, _i, _i]),
     "cmtts_vocoder_forward_windows": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _f, _vp, _sz, _vp]),
+    "cmtts_resampler_create": (_i, [_i, _i, _vp, _i, C.POINTER(_vp)]),
+    "cmtts_resampler_destroy": (None, [_vp]),
+    "cmtts_resampler_half_width": (_i, [_vp]),
+    "cmtts_resample_encode": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _f, _vp, _i64, _vp]),
+    "cmtts_vocoder_forward_windows_f32": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "cmtts_profile_begin": (_i, [_i, _i]),
     "cmtts_set_fused_resblock": (_i, [_i]),
     "cmtts_set_persistent_denoiser": (_i, [_i]),

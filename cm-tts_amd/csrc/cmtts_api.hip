@@ -25,6 +25,7 @@
 #include "attention.h"
 #include "text_state.h"
 #include "stream_windows.h"
+#include "resample.h"
 #include "noise_philox.h"
 
 namespace {
@@ -3135,6 +3136,159 @@ int cmtts_vocoder_forward_windows(cmtts_vocoder* v, const float* mel_ct, int B, 
                                                   max_wav_value, pcm, (void*)s);
     if (rc == -2) return fail(CMTTS_E_UNSUPPORTED, "cmtts_vocoder_forward_windows: conv_post kernel wider than 7");
     if (rc != 0) return fail(CMTTS_E_HIP, "conv_post windows launch failed");
+    return 0;
+}
+// Host copy of an int32 table that is device or page-locked host memory (the contract of cmtts_vocoder_forward_windows): a host
+// table is read in place, a device table is read back on `s`, which synchronises it.  *on_host tells which it was.
+static int fetch_table(const char* who, const void* table, void* host_copy, size_t bytes, hipStream_t s, bool* on_host) {
+    hipPointerAttribute_t at{};
+    const bool known = hipPointerGetAttributes(&at, table) == hipSuccess;
+    if (!known) (void)hipGetLastError();
+    *on_host = known && at.type == hipMemoryTypeHost;
+    const bool on_dev = known && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeUnified);
+    if (!*on_host && !on_dev) return fail(CMTTS_E_INVALID, std::string(who) + ": the table must be device or page-locked host memory");
+    if (*on_host) {
+        memcpy(host_copy, table, bytes);
+    } else {
+        HIPCHK(hipMemcpyAsync(host_copy, table, bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return 0;
+}
+int cmtts_vocoder_forward_windows_f32(cmtts_vocoder* v, const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, int core,
+                                      int margin_frames, float* wav_rows, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "cmtts_vocoder_forward_windows_f32";
+    if (!v || !v->finalized) return fail(CMTTS_E_INVALID, "vocoder not finalized");
+    if (!mel_ct || !windows || !wav_rows || !ws) return fail(CMTTS_E_INVALID, std::string(who) + ": null argument");
+    if (B <= 0 || T <= 0 || N <= 0 || Tw <= 0 || core <= 0) return fail(CMTTS_E_INVALID, std::string(who) + ": B, T, N, Tw and core must be positive");
+    if (Tw > T) return fail(CMTTS_E_INVALID, std::string(who) + ": Tw > T");
+    if (margin_frames < 0 || (Tw != T && (long)core + 2L * margin_frames > Tw))
+        return fail(CMTTS_E_INVALID, std::string(who) + ": margin_frames outside [0, (Tw - core) / 2] of a window narrower than T");
+    if (ws_bytes < cmtts_vocoder_windows_workspace_bytes(v, N, Tw)) return fail(CMTTS_E_WORKSPACE, std::string(who) + ": workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<StreamWindow> tab(N);
+    bool on_host = false;
+    CHK(fetch_table(who, windows, tab.data(), (size_t)N * sizeof(StreamWindow), s, &on_host));
+    for (int n = 0; n < N; ++n) {
+        const StreamWindow& w = tab[n];
+        char msg[200];
+        const char* bad = w.b < 0 || w.b >= B                                   ? "utterance outside [0, B)"
+                          : w.start < 0 || (long)w.start + Tw > T              ? "window outside [0, T)"
+                          : w.core_len <= 0 || w.core_len > core               ? "core_len outside [1, core]"
+                          : w.core_off < 0 || (long)w.core_off + w.core_len > Tw ? "core_off + core_len > Tw"
+                                                                                  : nullptr;
+        if (bad) {
+            snprintf(msg, sizeof msg, "%s: window %d (%d, %d, %d, %d): %s", who, n, w.b, w.start, w.core_off, w.core_len, bad);
+            return fail(CMTTS_E_INVALID, msg);
+        }
+    }
+    Carver cv(ws);
+    float* mel_w = cv.take<float>((size_t)N * 80 * Tw);
+    StreamWindow* win = cv.take<StreamWindow>(N);
+    void* gws = cv.base + ((cv.off + 255) & ~(size_t)255);
+    HIPCHK(hipMemcpyAsync(win, windows, (size_t)N * sizeof(StreamWindow), on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    if (cmtts_launch_mel_window_gather(mel_ct, 80, T, win, N, Tw, mel_w, (void*)s) != 0) return fail(CMTTS_E_HIP, "mel window gather launch failed");
+    const float* x = nullptr;
+    int ch = 0, Ti = 0, ld = 0;
+    if (const int rc = vocoder_generator(v, mel_w, N, Tw, gws, s, &x, &ch, &Ti, &ld)) return rc;
+    long hop = 1;
+    for (int i = 0; i < 4; ++i) hop *= v->up_rate[i];
+    // x = leaky_relu(xs / 3) [slope 0.01] -> conv_post -> tanh, core and margin columns only, fp32
+    const int rc = cmtts_launch_conv_post_windows_f32(x, v->post_w, v->post_b, 3.0f, 0.01f, win, N, ch, Ti, ld, v->post_k, (int)hop, core,
+                                                      margin_frames, wav_rows, (void*)s);
+    if (rc == -2) return fail(CMTTS_E_UNSUPPORTED, std::string(who) + ": conv_post kernel wider than 7");
+    if (rc != 0) return fail(CMTTS_E_HIP, "conv_post windows launch failed");
+    return 0;
+}
+
+// ---- output sample rates and encodings (resample.hip)
+struct cmtts_resampler {
+    int L = 0, M = 0, half = 0, R = 0;
+    float* table = nullptr;                 // [L][2 R + 1]
+    ResampleSegment* seg = nullptr;         // the validated table of the call in flight
+    int seg_cap = 0;
+};
+int cmtts_resampler_create(int L, int M, const float* taps_host, int half, cmtts_resampler** out) {
+    if (!taps_host || !out) return fail(CMTTS_E_INVALID, "cmtts_resampler_create: null argument");
+    if (L <= 0 || M <= 0 || half < 0) return fail(CMTTS_E_INVALID, "cmtts_resampler_create: L and M must be positive, half >= 0");
+    if (std::__gcd(L, M) != 1) return fail(CMTTS_E_INVALID, "cmtts_resampler_create: L and M must be coprime");
+    const long R = ((long)half + L - 1) / L;
+    if ((long)L * (2 * R + 1) > RS_MAX_TABLE) return fail(CMTTS_E_UNSUPPORTED, "cmtts_resampler_create: the tap table [L][2 R + 1] exceeds 65536 floats");
+    if (((long)(RS_TILE - 1) * M) / L + 2 * R + 2 > RS_MAX_SPAN)
+        return fail(CMTTS_E_UNSUPPORTED, "cmtts_resampler_create: a tile of 256 outputs spans more than 8192 source samples");
+    const size_t nt = 2 * (size_t)half + 1;
+    float *taps = nullptr, *table = nullptr;
+    HIPCHK(hipMalloc(&taps, nt * sizeof(float)));
+    if (hipMalloc(&table, (size_t)L * (2 * R + 1) * sizeof(float)) != hipSuccess) {
+        (void)hipFree(taps);
+        return fail(CMTTS_E_HIP, "cmtts_resampler_create: hipMalloc failed");
+    }
+    hipError_t e = hipMemcpy(taps, taps_host, nt * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && cmtts_launch_resample_table(taps, L, half, (int)R, table, nullptr) != 0) e = hipErrorLaunchFailure;
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    (void)hipFree(taps);
+    if (e != hipSuccess) {
+        (void)hipFree(table);
+        return fail(CMTTS_E_HIP, std::string("cmtts_resampler_create: ") + hipGetErrorString(e));
+    }
+    cmtts_resampler* r = new cmtts_resampler;
+    r->L = L; r->M = M; r->half = half; r->R = (int)R; r->table = table;
+    *out = r;
+    return 0;
+}
+void cmtts_resampler_destroy(cmtts_resampler* r) {
+    if (!r) return;
+    if (r->table) (void)hipFree(r->table);
+    if (r->seg) (void)hipFree(r->seg);
+    delete r;
+}
+int cmtts_resampler_half_width(const cmtts_resampler* r) {
+    if (!r) return fail(CMTTS_E_INVALID, "cmtts_resampler_half_width: null argument");
+    return r->R;
+}
+int cmtts_resample_encode(cmtts_resampler* r, const float* wav, int rows, int64_t ld, const int32_t* segments, int N, int encoding,
+                          float max_wav_value, void* out, int64_t out_ld, void* stream) {
+    const char* who = "cmtts_resample_encode";
+    if (!r || !wav || !segments || !out) return fail(CMTTS_E_INVALID, std::string(who) + ": null argument");
+    if (rows <= 0 || ld <= 0 || N <= 0 || N > 65535 || out_ld <= 0)
+        return fail(CMTTS_E_INVALID, std::string(who) + ": rows, ld, N and out_ld must be positive (N <= 65535)");
+    if (encoding < CMTTS_ENC_F32 || encoding > CMTTS_ENC_ALAW) return fail(CMTTS_E_INVALID, std::string(who) + ": unknown encoding");
+    if (!(max_wav_value > 0.f && max_wav_value <= 32768.f)) return fail(CMTTS_E_INVALID, std::string(who) + ": max_wav_value outside (0, 32768]");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<ResampleSegment> tab(N);
+    bool on_host = false;
+    CHK(fetch_table(who, segments, tab.data(), (size_t)N * sizeof(ResampleSegment), s, &on_host));
+    const long L = r->L, M = r->M, half = r->half;
+    auto fdiv = [](long a, long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };          // floor(a / b), b > 0
+    for (int n = 0; n < N; ++n) {
+        const ResampleSegment& g = tab[n];
+        const char* bad = nullptr;
+        if (g.row < 0 || g.row >= rows) bad = "source row outside [0, rows)";
+        else if (g.n_valid < 0) bad = "negative sample count";
+        else if (g.m0 < 0 || g.m1 < g.m0) bad = "m0 < 0 or m1 < m0";
+        else if ((long)g.m1 > ((long)g.n_valid * L + M - 1) / M) bad = "m1 beyond ceil(n L / M)";
+        else if ((long)g.m1 - g.m0 > out_ld) bad = "more outputs than out_ld";
+        else if (g.m1 > g.m0) {
+            const long lo = std::max(-fdiv(-((long)g.m0 * M - half), L), 0L);                  // ceil((m0 M - half) / L)
+            const long hi = std::min(fdiv(((long)g.m1 - 1) * M + half, L), (long)g.n_valid - 1);
+            if (lo <= hi && (lo < g.origin || hi >= (long)g.origin + ld)) bad = "the row does not hold the source samples these outputs need";
+        }
+        if (bad) {
+            char msg[240];
+            snprintf(msg, sizeof msg, "%s: segment %d (%d, %d, %d, %d, %d): %s", who, n, g.row, g.origin, g.m0, g.m1, g.n_valid, bad);
+            return fail(CMTTS_E_INVALID, msg);
+        }
+    }
+    if (N > r->seg_cap) {       // hipFree waits for the device: no call in flight still reads the old buffer
+        if (r->seg) (void)hipFree(r->seg);
+        r->seg = nullptr; r->seg_cap = 0;
+        const int cap = std::max(64, N);
+        HIPCHK(hipMalloc(&r->seg, (size_t)cap * sizeof(ResampleSegment)));
+        r->seg_cap = cap;
+    }
+    HIPCHK(hipMemcpyAsync(r->seg, segments, (size_t)N * sizeof(ResampleSegment), on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    const int rc = cmtts_launch_resample_encode(wav, (long)ld, r->seg, N, r->table, r->L, r->M, r->R, encoding, max_wav_value, out, (long)out_ld, (void*)s);
+    if (rc != 0) return fail(CMTTS_E_HIP, "resample_encode launch failed");
     return 0;
 }
 int cmtts_internal_mel_window_gather(const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, float* out, void* stream) {

@@ -19,6 +19,10 @@ int cmtts_launch_mel_window_gather(const float* mel_ct, int M, int T, const Stre
 // 0 after that.  The same tap / channel order as conv_post_kernel and the same cast as wav_to_int16_kernel (kernels.hip).
 int cmtts_launch_conv_post_windows(const float* x, const float* w, const float* bias, float pre_div, float slope, const StreamWindow* win,
                                    int N, int C, int Ti, int ld, int KW, int hop, int core, float max_wav, int16_t* pcm, void* stream);
+// The same last layer as fp32 with margins: wav [N][(core + 2 margin) * hop], row n = tanh(conv_post(.)) on the window-local frames
+// [max(core_off - margin, 0), min(core_off + core_len + margin, Tw)), then zeros.  Bitwise the values the int16 kernel casts.
+int cmtts_launch_conv_post_windows_f32(const float* x, const float* w, const float* bias, float pre_div, float slope, const StreamWindow* win,
+                                       int N, int C, int Ti, int ld, int KW, int hop, int core, int margin, float* wav, void* stream);
 #ifdef __cplusplus
 }
 #endif

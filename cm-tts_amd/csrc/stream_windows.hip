@@ -136,6 +136,106 @@ __global__ __launch_bounds__(256) void conv_post_windows_kernel(const float* __r
     }
 }
 
+// conv_post_windows_kernel with a float, margin-carrying output (cmtts_vocoder_forward_windows_f32: the input of the resampler,
+// which needs the samples up to one filter half-width beyond the core): the same accumulation — channel / tap order, fmaf, tanhf,
+// the same loads — written as fp32 for the window-local frames [core_off - margin, core_off + core_len + margin) clipped to the
+// window, row pitch (core + 2 margin) * hop, zeros after.  Kept apart from the int16 kernel, which stays as it is.
+template <bool V4>
+__global__ __launch_bounds__(256) void conv_post_windows_f32_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                const float* __restrict__ bias, float pre_div, float slope,
+                                                                const StreamWindow* __restrict__ win, int C, int Ti, int ld, int KW,
+                                                                int hop, int core, int margin, float* __restrict__ wav) {
+    extern __shared__ float wsh[];
+    for (int i = threadIdx.x; i < C * KW; i += 256) wsh[i] = w[i];
+    __syncthreads();
+    const int n = blockIdx.y;
+    const long row = (long)(core + 2 * margin) * hop;
+    const long j0 = ((long)blockIdx.x * 256 + threadIdx.x) * PV;
+    if (j0 >= row) return;
+    float* out = wav + n * row;
+    const StreamWindow wd = win[n];
+    const int Tw = Ti / hop;
+    const int f_lo = max(wd.core_off - margin, 0), f_hi = min(wd.core_off + wd.core_len + margin, Tw);
+    const long jn = (long)(f_hi - f_lo) * hop;        // samples of this window's core and margins; the rest of the row is zero
+    if (j0 >= jn) {
+#pragma unroll
+        for (int v = 0; v < PV; ++v)
+            if (j0 + v < row) out[j0 + v] = 0.f;
+        return;
+    }
+    const int t0 = f_lo * hop + (int)j0;               // window-local sample of the first output
+    const int pad = KW / 2;
+    float acc[PV];
+#pragma unroll
+    for (int v = 0; v < PV; ++v) acc[v] = 0.f;
+    const float* xb = x + (long)n * C * ld;
+    if constexpr (V4) {
+        const int tl = max(t0 - 4, 0), tr = min(t0 + 4, ((Ti + 3) & ~3) - 4);
+        constexpr int CU = 4;
+        for (int c0 = 0; c0 < C; c0 += CU) {
+            float4 Lq[CU], Mq[CU], Rq[CU];
+#pragma unroll
+            for (int u = 0; u < CU; ++u) {
+                const float* xr = xb + (long)min(c0 + u, C - 1) * ld;
+                Lq[u] = *reinterpret_cast<const float4*>(xr + tl);
+                Mq[u] = *reinterpret_cast<const float4*>(xr + t0);
+                Rq[u] = *reinterpret_cast<const float4*>(xr + tr);
+            }
+#pragma unroll
+            for (int u = 0; u < CU; ++u) {
+                if (c0 + u >= C) break;
+                const float raw[12] = {Lq[u].x, Lq[u].y, Lq[u].z, Lq[u].w, Mq[u].x, Mq[u].y, Mq[u].z, Mq[u].w, Rq[u].x, Rq[u].y, Rq[u].z, Rq[u].w};
+                float xv[PV + PKW_MAX - 1];
+#pragma unroll
+                for (int q = 0; q < PV + PKW_MAX - 1; ++q) {
+                    const int tt = t0 + q - pad;
+                    const int ri = q - pad + 4;
+                    float v = (q < PV + KW - 1 && tt >= 0 && tt < Ti && ri >= 0 && ri < 12) ? raw[ri < 0 ? 0 : (ri > 11 ? 11 : ri)] : 0.f;
+                    if (pre_div != 1.0f) v = v / pre_div;
+                    xv[q] = v > 0.f ? v : v * slope;
+                }
+#pragma unroll
+                for (int k = 0; k < PKW_MAX; ++k) {
+                    if (k < KW) {
+                        const float wk = wsh[(c0 + u) * KW + k];
+#pragma unroll
+                        for (int v = 0; v < PV; ++v) acc[v] = fmaf(wk, xv[v + k], acc[v]);
+                    }
+                }
+            }
+        }
+    } else {
+        for (int c = 0; c < C; ++c) {
+            const float* xr = xb + (long)c * ld;
+            float xv[PV + PKW_MAX - 1];
+#pragma unroll
+            for (int q = 0; q < PV + PKW_MAX - 1; ++q) {
+                const int tt = t0 + q - pad;
+                float v = (q < PV + KW - 1 && tt >= 0 && tt < Ti) ? xr[tt] : 0.f;
+                if (pre_div != 1.0f) v = v / pre_div;
+                xv[q] = v > 0.f ? v : v * slope;
+            }
+#pragma unroll
+            for (int k = 0; k < PKW_MAX; ++k) {
+                if (k < KW) {
+                    const float wk = wsh[c * KW + k];
+#pragma unroll
+                    for (int v = 0; v < PV; ++v) acc[v] = fmaf(wk, xv[v + k], acc[v]);
+                }
+            }
+        }
+    }
+    const float bs = bias[0];
+#pragma unroll
+    for (int v = 0; v < PV; ++v) {
+        if (j0 + v < jn) {
+            out[j0 + v] = tanhf(acc[v] + bs);
+        } else if (j0 + v < row) {
+            out[j0 + v] = 0.f;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int cmtts_launch_mel_window_gather(const float* mel_ct, int M, int T, const StreamWindow* win, int N, int Tw, float* out, void* stream) {
@@ -158,5 +258,22 @@ extern "C" int cmtts_launch_conv_post_windows(const float* x, const float* w, co
     else
         hipLaunchKernelGGL(conv_post_windows_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, x, w, bias, pre_div, slope, win, C, Ti, ld,
                            KW, hop, core, max_wav, pcm);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+extern "C" int cmtts_launch_conv_post_windows_f32(const float* x, const float* w, const float* bias, float pre_div, float slope, const StreamWindow* win,
+                                                  int N, int C, int Ti, int ld, int KW, int hop, int core, int margin, float* wav, void* stream) {
+    if (KW > PKW_MAX || KW / 2 > 4) return -2;
+    if (N <= 0 || core <= 0 || margin < 0) return 0;
+    const dim3 grid(cdiv((long)(core + 2 * margin) * hop, 256 * PV), N);
+    const size_t lds = (size_t)C * KW * sizeof(float);
+    // every window-local start f_lo * hop + 4 i is a multiple of 4 when hop is
+    const bool v4 = (hop & 3) == 0 && (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && ld >= ((Ti + 3) & ~3) && Ti >= 4;
+    if (v4)
+        hipLaunchKernelGGL(conv_post_windows_f32_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, x, w, bias, pre_div, slope, win, C, Ti,
+                           ld, KW, hop, core, margin, wav);
+    else
+        hipLaunchKernelGGL(conv_post_windows_f32_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, x, w, bias, pre_div, slope, win, C, Ti,
+                           ld, KW, hop, core, margin, wav);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -1050,10 +1050,76 @@ def vocoder_infer_device(mels, vocoder, max_wav_value=32768.0):
     return pcm
 
 
-def vocoder_infer(mels, vocoder, model_config=None, preprocess_config=None, lengths=None, max_wav_value=32768.0):
-    """utils/model.py:187-205: mels [B,80,T] -> list of int16 numpy arrays trimmed to `lengths`."""
+class _Resampler:
+    """One (L, M) resampler of a vocoder: the float32 taps of cmtts_amd.resample.design_taps handed to cmtts_resampler_create."""
+
+    def __init__(self, lib, device, L, M):
+        from . import resample as rs
+        self.lib, self.L, self.M = lib, L, M
+        self.taps, self.half = rs.design_taps(L, M)
+        self.R = rs.half_width(L, self.half)
+        self._h = C.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(lib.cmtts_resampler_create(L, M, self.taps.ctypes.data_as(C.c_void_p), self.half, C.byref(self._h)))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and C is not None:
+            self.lib.cmtts_resampler_destroy(h)
+            self._h = None
+
+    def out_len(self, n):
+        return -(-int(n) * self.L // self.M)
+
+
+def _output_format(vocoder, sample_rate, encoding):
+    """None for the native format (the vocoder's rate, "s16": the existing path, wrap included), else (resampler, encoding code,
+    torch dtype).  The filter of a rate is designed once per vocoder (cmtts_amd.resample.design_taps)."""
+    from . import resample as rs
+    if encoding not in rs.ENCODINGS:
+        raise ValueError(f"encoding {encoding!r}: expected one of {sorted(rs.ENCODINGS)}")
+    native = rs.NATIVE_RATE
+    rate = native if sample_rate is None else int(sample_rate)
+    if rate == native and encoding == "s16":
+        return None
+    L, M = rs.ratio(native, rate)
+    cache = vocoder.__dict__.setdefault("_resamplers", {})
+    if (L, M) not in cache:
+        cache[(L, M)] = _Resampler(vocoder.lib, vocoder.device, L, M)
+    dtype = {"f32": torch.float32, "s16": torch.int16, "mulaw": torch.uint8, "alaw": torch.uint8}[encoding]
+    return cache[(L, M)], rs.ENCODINGS[encoding], dtype
+
+
+def _resample_encode(lib, rsm, wav, seg_tab, enc, dtype, max_wav_value, out_ld):
+    """cmtts_resample_encode on the current stream: wav fp32 [rows, ld] (device), seg_tab int32 [N, 5] (pinned host or device)."""
+    N = seg_tab.shape[0]
+    out = torch.empty(N, out_ld, dtype=dtype, device=wav.device)
+    _lib.check(lib.cmtts_resample_encode(rsm._h, _ptr(wav), wav.shape[0], wav.shape[1], _ptr(seg_tab), N, enc, float(max_wav_value),
+                                         _ptr(out), out_ld, _stream()))
+    return out
+
+
+def vocoder_infer(mels, vocoder, model_config=None, preprocess_config=None, lengths=None, max_wav_value=32768.0,
+                  sample_rate=None, encoding="s16"):
+    """utils/model.py:187-205: mels [B,80,T] -> list of int16 numpy arrays trimmed to `lengths`.
+    sample_rate / encoding: another output rate (8000, 16000, 24000, 32000, 44100, 48000) and / or "f32", "s16",
+    "mulaw", "alaw" — resampled and encoded on the device by one cmtts_resample_encode after the unchanged generator; `lengths` still
+    counts SOURCE samples, row b comes back with ceil(lengths[b] * L / M) samples of dtype float32 / int16 / uint8, and "s16" saturates.
+    The defaults (None or the native 22 050 Hz, "s16") are the reference's cast, wrap included."""
     if preprocess_config is not None:
         max_wav_value = preprocess_config["preprocessing"]["audio"]["max_wav_value"]
+    fmt = _output_format(vocoder, sample_rate, encoding)
+    if fmt is not None:
+        rsm, enc, dtype = fmt
+        wavs = vocoder(mels).squeeze(1)
+        B, n = wavs.shape
+        lens = [n] * B if lengths is None else [min(max(int(v), 0), n) for v in lengths]
+        tab = torch.tensor([(b, 0, 0, rsm.out_len(lens[b]), lens[b]) for b in range(B)], dtype=torch.int32).pin_memory()
+        with torch.cuda.device(wavs.device):
+            out = _resample_encode(vocoder.lib, rsm, wavs, tab, enc, dtype, max_wav_value, max(rsm.out_len(n), 1))
+        arr = out.cpu().numpy()          # synchronises: the pinned table is free again
+        check_async_error()
+        return [arr[b, : rsm.out_len(lens[b])] for b in range(B)]
     pcm = vocoder_infer_device(mels, vocoder, max_wav_value)
     out = [w for w in pcm.cpu().numpy()]
     check_async_error()          # the D2H copy synchronised: a timeout in the launches that produced `mels` is raised here
@@ -1123,14 +1189,20 @@ def plan_stream_windows(T, mel_lens, chunk_frames=STREAM_CHUNK_FRAMES, halo=13):
     return rounds
 
 
-def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_FRAMES, max_wav_value=32768.0):
+def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_FRAMES, max_wav_value=32768.0,
+                         sample_rate=None, encoding="s16"):
     """vocoder_infer, streamed: mels [B,80,T] -> a generator of (utterance, sample_offset, pcm int16 numpy, is_last), round by round
     (plan_stream_windows; lengths = mel FRAMES per utterance, default T — vocoder_infer's `lengths` count samples).  Concatenated per
     utterance the chunks are vocoder_infer(mels, lengths=mel_len * hop)'s output: bitwise with the direct fp32 form ("winograd" 0),
     within the conv forms' rounding otherwise.  Round r + 1 is enqueued on the current stream before round r's chunks are
-    handed back; each round's int16 rows go to pinned host memory on a copy stream, so that copy overlaps the next round's generator."""
+    handed back; each round's int16 rows go to pinned host memory on a copy stream, so that copy overlaps the next round's generator.
+    sample_rate / encoding (vocoder_infer): the windows reach one frame further (halo H + 1), each round's last layer
+    writes fp32 rows with one frame of margin (cmtts_vocoder_forward_windows_f32) and one cmtts_resample_encode turns the round's cores
+    into chunks of the output format; offsets then count OUTPUT samples, an utterance's chunks concatenate to
+    ceil(mel_len * hop * L / M) samples and are bitwise vocoder_infer(..., sample_rate, encoding)'s under the same condition."""
     vocoder._require()
     lib, dev = vocoder.lib, vocoder.device
+    fmt = _output_format(vocoder, sample_rate, encoding)
     x = _f32(mels, dev)
     B, M, T = x.shape
     lens = [T] * B if lengths is None else [int(n) for n in lengths]
@@ -1140,7 +1212,10 @@ def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_
     if halo < 0:
         _lib.check(halo)
     hop = vocoder.h.hop
-    rounds = plan_stream_windows(T, lens, chunk_frames, halo)
+    if fmt is not None and fmt[0].R > hop:
+        raise ValueError(f"vocoder_infer_stream: the filter's half-width {fmt[0].R} exceeds one frame ({hop} samples)")
+    # the resampler needs R <= hop samples beyond a core on each side: one more frame of halo, one frame of margin in the float rows
+    rounds = plan_stream_windows(T, lens, chunk_frames, halo if fmt is None else halo + 1)
     if not rounds:
         return
     with torch.cuda.device(dev):
@@ -1152,12 +1227,24 @@ def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_
         def enqueue(r):
             N = len(r.windows)
             tab = torch.tensor(r.windows, dtype=torch.int32).pin_memory()      # read in place by the call: kept until `done`
-            pcm = torch.empty(N, r.core * hop, dtype=torch.int16, device=dev)
-            _lib.check(lib.cmtts_vocoder_forward_windows(vocoder._h, _ptr(x), B, T, _ptr(tab), N, r.Tw, r.core, _ptr(pcm),
-                                                         float(max_wav_value), _ptr(ws), nb, _stream()))
+            if fmt is None:
+                pcm = torch.empty(N, r.core * hop, dtype=torch.int16, device=dev)
+                _lib.check(lib.cmtts_vocoder_forward_windows(vocoder._h, _ptr(x), B, T, _ptr(tab), N, r.Tw, r.core, _ptr(pcm),
+                                                             float(max_wav_value), _ptr(ws), nb, _stream()))
+            else:
+                rsm, enc, dtype = fmt
+                rows = torch.empty(N, (r.core + 2) * hop, dtype=torch.float32, device=dev)
+                _lib.check(lib.cmtts_vocoder_forward_windows_f32(vocoder._h, _ptr(x), B, T, _ptr(tab), N, r.Tw, r.core, 1, _ptr(rows),
+                                                                 _ptr(ws), nb, _stream()))
+                # row n starts at frame max(core start - 1, window start); the outputs of the core [f0, f0 + cl) come from the absolute m
+                segs = [(n, max(start + off - 1, start) * hop, rsm.out_len((start + off) * hop), rsm.out_len((start + off + cl) * hop),
+                         lens[b] * hop) for n, (b, start, off, cl) in enumerate(r.windows)]
+                seg_tab = torch.tensor(segs, dtype=torch.int32).pin_memory()
+                pcm = _resample_encode(lib, rsm, rows, seg_tab, enc, dtype, max_wav_value, max(m1 - m0 for _, _, m0, m1, _ in segs))
+                tab = (tab, seg_tab, segs)
             ready = torch.cuda.Event()
             ready.record(comp)
-            host = torch.empty(N, r.core * hop, dtype=torch.int16, pin_memory=True)
+            host = torch.empty(pcm.shape, dtype=pcm.dtype, pin_memory=True)
             with torch.cuda.stream(copy):
                 copy.wait_event(ready)
                 host.copy_(pcm, non_blocking=True)
@@ -1178,7 +1265,11 @@ def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_
                 arr = host.numpy()
                 for n, (b, start, off, cl) in enumerate(r.windows):
                     f0 = start + off
-                    yield b, f0 * hop, arr[n, : cl * hop].copy(), f0 + cl >= lens[b]
+                    if fmt is None:
+                        yield b, f0 * hop, arr[n, : cl * hop].copy(), f0 + cl >= lens[b]
+                    else:
+                        m0, m1 = _tab[2][n][2:4]
+                        yield b, m0, arr[n, : m1 - m0].copy(), f0 + cl >= lens[b]
         finally:
             # a consumer that stops early: the pinned tables of rounds still in flight are read by their calls' copies
             for p in pending:
@@ -1187,12 +1278,13 @@ def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_
 
 def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=None, speakers=None, n_steps=4, noise=None,
                       chunk_frames=STREAM_CHUNK_FRAMES, generator=None, max_wav_value=32768.0,
-                      p_control=1.0, e_control=1.0, d_control=1.0, seeds=None):
+                      p_control=1.0, e_control=1.0, d_control=1.0, seeds=None, sample_rate=None, encoding="s16"):
     """Text -> streamed PCM: the duration net and the T-step sampler exactly as CMTotalTTSSynthesize.synthesize runs them (noise
     [n_noise, B, 1, T, 80] drawn as x0 = randn, then randn_like(x0) per further step, unless given), then vocoder_infer_stream on
     the mels trimmed to their predicted lengths.  Yields (utterance, sample_offset, pcm int16 numpy, is_last).
     p_control / e_control / d_control: numbers, [B] or [B, L] float32 tensors (DurationPitchSpeakerNet.forward).
-    seeds: int64 [B] utterance seeds or one int — seeded noise generated by the sampler (sample_with_cond), in place of noise / generator."""
+    seeds: int64 [B] utterance seeds or one int — seeded noise generated by the sampler (sample_with_cond), in place of noise / generator.
+    sample_rate / encoding: the output format (vocoder_infer_stream); offsets then count output samples."""
     if seeds is not None and noise is not None:
         raise ValueError("synthesize_stream: give noise or seeds, not both")
     out = model.duration_pitch_energy_net(speakers=speakers, texts=texts, src_lens=src_lens, spker_embeds=spker_embeds,
@@ -1206,7 +1298,8 @@ def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=
         noise = _draw_sampler_noise(generator or DummyGenerator(), B, T, cfg.n_mels, draws, model.device)
     mel = sample_with_cond(model, out["cond_ct"], out["speaker_emb"], n_steps, noise, factors=out.get("cond_factors"), seeds=seeds)
     mel_lens = out["mel_lens"].cpu().tolist()
-    yield from vocoder_infer_stream(mel.transpose(1, 2), vocoder, mel_lens, chunk_frames, max_wav_value)
+    yield from vocoder_infer_stream(mel.transpose(1, 2), vocoder, mel_lens, chunk_frames, max_wav_value, sample_rate=sample_rate,
+                                    encoding=encoding)
 
 
 def synth_samples(args, targets, predictions, vocoder, model_config, preprocess_config, path, diffusion=None):

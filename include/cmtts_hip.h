@@ -65,7 +65,8 @@ const char* cmtts_version(void);
  * cmtts_vocoder_forward_windows);
  * 8 — options only: cmtts_model_set_option / cmtts_vocoder_set_option "batch_invariant" (a host detects support here);
  * still 8 — cmtts_set_control_tables (per-phoneme control tables) is a new entry point and a new struct: no existing layout or
- * signature changes, so the number stays; a host detects it by looking the symbol up (dlsym).
+ * signature changes, so the number stays; a host detects it by looking the symbol up (dlsym).  Likewise the resampler
+ * (cmtts_resampler_*, cmtts_resample_encode) and cmtts_vocoder_forward_windows_f32: entry points only, still 8.
  * A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
  * against before it passes a struct (cmtts_amd/_lib.py does at load time). */
 #define CMTTS_ABI_VERSION 8
@@ -349,6 +350,43 @@ int cmtts_vocoder_halo_frames(const cmtts_vocoder* v);
 size_t cmtts_vocoder_windows_workspace_bytes(const cmtts_vocoder* v, int N, int Tw);
 int cmtts_vocoder_forward_windows(cmtts_vocoder* v, const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, int core,
                                   int16_t* pcm, float max_wav_value, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- output sample rates and encodings (the definition in executable form: cmtts_amd/resample.py).
+ * A resampler is a rational L / M polyphase FIR (output rate = input rate * L / M, L and M coprime) whose taps come from the HOST, so the
+ * filter has exactly one definition: taps_host fp32 [2 half + 1], symmetric about index half, on the x L grid.  Output m of an utterance
+ * x[0 .. n) is y[m] = sum_j x[j] * taps[m M - j L + half] over the j with a tap, j ascending, fp32 fmaf from 0, x zero outside [0, n);
+ * there are ceil(n L / M) outputs.  R = ceil(half / L) = cmtts_resampler_half_width(r) is the filter's half-width in source samples.
+ * cmtts_resampler_create builds the phase-major tap table [L][2 R + 1] on the current device (synchronises the null stream once);
+ * CMTTS_E_UNSUPPORTED when the table holds more than 65536 floats or 256 outputs span more than 8192 source samples.
+ * cmtts_resample_encode: wav fp32 [rows][ld] (device); segments int32 [N][5] = (source row, absolute sample index of that row's element
+ * 0, m0, m1, the utterance's valid sample count n): output row i holds the encoded outputs [m0, m1) of its utterance — which need
+ * source samples [ceil((m0 M - half) / L), floor(((m1 - 1) M + half) / L)] clipped to [0, n), all of which the row must hold
+ * (origin <= first, last < origin + ld) — then zeros up to out_ld.  The phase comes from the absolute m and the summation order does not
+ * depend on the segment, so a wave resampled in pieces is BITWISE the wave resampled whole.  out [N][out_ld]: float (CMTTS_ENC_F32),
+ * int16 (CMTTS_ENC_S16: (int)(y * max_wav_value) truncated toward zero as cmtts_wav_to_int16 does, but SATURATED to [-32768, 32767] where
+ * that cast wraps) or uint8 (CMTTS_ENC_MULAW / CMTTS_ENC_ALAW: ITU-T G.711 of that int16 value).
+ * The table may be device memory or page-locked host memory and is VALIDATED on the host before anything is launched, with the contract
+ * of cmtts_vocoder_forward_windows (CMTTS_E_INVALID and nothing launched; a device table is read back first, which synchronises `stream`;
+ * a page-locked host table is read in place and copied on `stream`, so the caller keeps it unchanged until the call's work has completed).
+ * The copy lands in a buffer the resampler owns: calls on one resampler are issued on one stream (or ordered by the caller).
+ * cmtts_vocoder_forward_windows_f32: cmtts_vocoder_forward_windows with a float last layer that carries margins — wav_rows fp32
+ * [N][(core + 2 margin_frames) * 256]: row n holds tanh(conv_post(.)) for the window-local frames [max(core_off - margin_frames, 0),
+ * min(core_off + core_len + margin_frames, Tw)), bitwise the columns of cmtts_vocoder_forward's wav under the conditions above, then
+ * zeros.  0 <= margin_frames, and core + 2 margin_frames <= Tw unless Tw == T (a whole-tensor window).  Same table contract, same
+ * workspace (cmtts_vocoder_windows_workspace_bytes(v, N, Tw)).  With windows that reach H + 1 frames beyond their cores and margin_frames
+ * = 1 the rows hold what cmtts_resample_encode needs for the cores, since R <= 256. */
+#define CMTTS_ENC_F32 0
+#define CMTTS_ENC_S16 1
+#define CMTTS_ENC_MULAW 2
+#define CMTTS_ENC_ALAW 3
+typedef struct cmtts_resampler cmtts_resampler;
+int cmtts_resampler_create(int L, int M, const float* taps_host, int half, cmtts_resampler** out);
+void cmtts_resampler_destroy(cmtts_resampler* r);
+int cmtts_resampler_half_width(const cmtts_resampler* r);
+int cmtts_resample_encode(cmtts_resampler* r, const float* wav, int rows, int64_t ld, const int32_t* segments, int N, int encoding,
+                          float max_wav_value, void* out, int64_t out_ld, void* stream);
+int cmtts_vocoder_forward_windows_f32(cmtts_vocoder* v, const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, int core,
+                                      int margin_frames, float* wav_rows, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- measurement hook (no reference counterpart; the reference's only perf tooling is the
  * wall-clock Timer of p_rtf_cm.py:64-108): HIP events recorded on the launch stream around every
