@@ -285,6 +285,30 @@ def internal_noise_bits(seeds, B, T, M, first_draw, n_draws, t0, bits, stream):
     return _noise_bits(seeds, int(B), int(T), int(M), int(first_draw), int(n_draws), int(t0), bits, stream)
 
 
+_pack_weights = None
+
+
+def internal_pack_weights(layout, kmajor, mode=0):
+    """csrc/internal_hooks.h: cmtts_internal_pack_weights — one of the host-side weight packers (csrc/weight_pack.h) on a float32 numpy array
+    kmajor [taps][K][M] (tests only; host memory, no GPU).  Returns the packed stream as a uint8 array, or None for an unknown layout or a
+    shape the packer does not cover."""
+    global _pack_weights
+    import numpy as np
+    load()
+    if _pack_weights is None:
+        _pack_weights = C.CDLL(LIB_PATH).cmtts_internal_pack_weights
+        _pack_weights.restype, _pack_weights.argtypes = _i, [C.c_char_p, _vp, _i, _i, _i, _i, _vp, _sz, C.POINTER(_sz)]
+    w = np.ascontiguousarray(kmajor, np.float32)
+    taps, K, M = w.shape
+    need = _sz(0)
+    if _pack_weights(layout.encode(), w.ctypes.data, taps, K, M, int(mode), None, 0, C.byref(need)) != 0:
+        return None
+    out = np.empty(need.value, np.uint8)
+    if _pack_weights(layout.encode(), w.ctypes.data, taps, K, M, int(mode), out.ctypes.data, out.nbytes, C.byref(need)) != 0:
+        return None
+    return out
+
+
 def backend():
     """"cffi" or "ctypes": which binding load() picked."""
     return "cffi" if isinstance(load(), _CffiLib) else "ctypes"

@@ -1,5 +1,5 @@
-// C ABI of the MI355X-native CM-TTS inference hot path (include/cmtts_hip.h): weight import
-// (re-pack + upload), workspace carving and the host-side launch sequences.  No allocation and no
+// C ABI of the MI355X-native CM-TTS inference hot path (include/cmtts_hip.h): the entry points, workspace carving and the
+// host-side launch sequences (weight import: import.hip; handles: model.h).  No allocation and no
 // host synchronisation after cmtts_finalize(); everything is enqueued on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/cmtts_hip.h"
+#include "model.h"
 #include "internal_hooks.h"
 #include "conv_args.h"
 #include "kernels.h"
@@ -28,409 +29,14 @@
 #include "resample.h"
 #include "noise_philox.h"
 
-namespace {
 
-thread_local std::string g_err;
+static thread_local std::string g_err;
 int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-#define HIPCHK(x)                                                                              \
-    do {                                                                                       \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess) return fail(CMTTS_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define CHK(x)                 \
-    do {                       \
-        int r_ = (x);          \
-        if (r_ != 0) return r_; \
-    } while (0)
 
-struct HostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-    int64_t dim(int i) const { return i < (int)shape.size() ? shape[i] : 1; }
-};
-
-struct PackedConv {
-    float* w = nullptr;     // device, [phase][tap][cin][ld]
-    float* bias = nullptr;  // device, [cout] (packed row order)
-    int cout = 0, cin = 0, taps = 0, ld = 0;
-    long tap_stride = 0, phase_stride = 0;
-};
-
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-struct Allocs {
-    std::vector<void*> ptrs;
-    int upload(const std::vector<float>& h, float** out) {
-        void* p = nullptr;
-        HIPCHK(hipMalloc(&p, h.size() * sizeof(float) + 256));
-        HIPCHK(hipMemcpy(p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-        ptrs.push_back(p);
-        *out = (float*)p;
-        return 0;
-    }
-    int upload_bytes(const void* h, size_t nbytes, void** out) {
-        void* p = nullptr;
-        HIPCHK(hipMalloc(&p, nbytes + 256));
-        HIPCHK(hipMemcpy(p, h, nbytes, hipMemcpyHostToDevice));
-        ptrs.push_back(p);
-        *out = p;
-        return 0;
-    }
-    void release() {
-        for (void* p : ptrs) (void)hipFree(p);
-        ptrs.clear();
-    }
-};
-
-// W [Cout][Cin][K] -> k-major [K][Cin][ld] with ld = round_up(Cout, 4); perm[p] = original row of packed row p
-int pack_conv(Allocs& al, const HostTensor& W, const HostTensor* bias, const std::vector<int>* perm, PackedConv* out,
-              std::vector<float>* host_copy = nullptr) {
-    const int Cout = (int)W.dim(0), Cin = (int)W.dim(1), K = (int)W.dim(2);
-    const int ld = round_up(Cout, 4);
-    std::vector<float> p((size_t)K * Cin * ld, 0.f);
-    for (int k = 0; k < K; ++k)
-        for (int ci = 0; ci < Cin; ++ci)
-            for (int r = 0; r < Cout; ++r) {
-                const int co = perm ? (*perm)[r] : r;
-                p[((size_t)k * Cin + ci) * ld + r] = W.data[((size_t)co * Cin + ci) * K + k];
-            }
-    CHK(al.upload(p, &out->w));
-    if (host_copy) *host_copy = p;
-    out->bias = nullptr;
-    if (bias) {
-        std::vector<float> b(Cout);
-        for (int r = 0; r < Cout; ++r) b[r] = bias->data[perm ? (*perm)[r] : r];
-        CHK(al.upload(b, &out->bias));
-    }
-    out->cout = Cout; out->cin = Cin; out->taps = K; out->ld = ld;
-    out->tap_stride = (long)Cin * ld;
-    out->phase_stride = 0;
-    return 0;
-}
-
-// ConvTranspose1d W [Cin][Cout][K], stride s -> polyphase [s][K/s][Cin][ld]: phase r uses taps k = r + s*q
-int pack_conv_transpose(Allocs& al, const HostTensor& W, const HostTensor& bias, int s, PackedConv* out,
-                        std::vector<float>* two_tap = nullptr) {
-    const int Cin = (int)W.dim(0), Cout = (int)W.dim(1), K = (int)W.dim(2);
-    const int Q = K / s, ld = round_up(Cout, 4);
-    if (two_tap && Q == 2) {   // the same weights as ONE two-tap conv with s * Cout stacked rows (row = phase * Cout + co): [2][Cin][s * Cout]
-        two_tap->assign((size_t)2 * Cin * s * Cout, 0.f);
-        for (int q = 0; q < 2; ++q)
-            for (int ci = 0; ci < Cin; ++ci)
-                for (int r = 0; r < s; ++r)
-                    for (int co = 0; co < Cout; ++co)
-                        (*two_tap)[((size_t)q * Cin + ci) * s * Cout + (size_t)r * Cout + co] = W.data[((size_t)ci * Cout + co) * K + (r + s * q)];
-    }
-    std::vector<float> p((size_t)s * Q * Cin * ld, 0.f);
-    for (int r = 0; r < s; ++r)
-        for (int q = 0; q < Q; ++q)
-            for (int ci = 0; ci < Cin; ++ci)
-                for (int co = 0; co < Cout; ++co)
-                    p[(((size_t)r * Q + q) * Cin + ci) * ld + co] = W.data[((size_t)ci * Cout + co) * K + (r + s * q)];
-    CHK(al.upload(p, &out->w));
-    CHK(al.upload(bias.data, &out->bias));
-    out->cout = Cout; out->cin = Cin; out->taps = Q; out->ld = ld;
-    out->tap_stride = (long)Cin * ld;
-    out->phase_stride = (long)Q * Cin * ld;
-    return 0;
-}
-
-// k-major packed weights [taps][K][M] -> MFMA A-fragment order [taps][K/8][M/32][64 lanes][4]:
-// element (lane, j) of k-group g, m-tile mt is P[tap][8g + 2j + (lane >> 5)][32 mt + (lane & 31)], i.e. the A
-// operand of v_mfma_f32_32x32x2_f32 for k-step j of that group (lane l supplies A[m = l & 31][k = l >> 5]).
-std::vector<float> to_fragment_order(const std::vector<float>& p, int taps, int K, int M) {
-    std::vector<float> f((size_t)taps * K * M);
-    const int G = K / 8, MTn = M / 32;
-    for (int tap = 0; tap < taps; ++tap)
-        for (int g = 0; g < G; ++g)
-            for (int mt = 0; mt < MTn; ++mt)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 4; ++j)
-                        f[((((size_t)tap * G + g) * MTn + mt) * 64 + lane) * 4 + j] =
-                            p[((size_t)tap * K + 8 * g + 2 * j + (lane >> 5)) * M + 32 * mt + (lane & 31)];
-    return f;
-}
-
-// Winograd F(2,3) form of a k = 3 conv for the persistent denoiser's WINO instances (denoiser_persist.hip): k-major packed weights
-// [3][K][M] -> transformed weights G0 = g0, G1 = (g0 + g1 + g2) / 2, G2 = (g0 - g1 + g2) / 2, G3 = g2 (formed in double, rounded once) as MFMA
-// A fragments [K/4 half-groups][M/32][2][64 lanes][4]: element q of fragment (hg, mt, ps) at lane l is transform 2 ps + (q >> 1) of
-// input channel 4 hg + 2 (q & 1) + (l >> 5), output row 32 mt + (l & 31).
-constexpr int WINO_PAD_HG = 4;        // half-groups of zero padding behind a layer's array: the kernel's weight ring runs a few stages past the end
-std::vector<float> to_wino_fragments(const std::vector<float>& p, int K, int M) {
-    std::vector<float> f((size_t)4 * K * M + (size_t)WINO_PAD_HG * (M / 32) * 2 * 64 * 4, 0.0f);
-    const int MTn = M / 32;
-    for (int hg = 0; hg < K / 4; ++hg)
-        for (int mt = 0; mt < MTn; ++mt)
-            for (int ps = 0; ps < 2; ++ps)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int q = 0; q < 4; ++q) {
-                        const int tr = 2 * ps + (q >> 1), k = 4 * hg + 2 * (q & 1) + (lane >> 5), mrow = 32 * mt + (lane & 31);
-                        const double g0 = p[((size_t)0 * K + k) * M + mrow], g1 = p[((size_t)1 * K + k) * M + mrow], g2 = p[((size_t)2 * K + k) * M + mrow];
-                        const double v = tr == 0 ? g0 : tr == 1 ? 0.5 * (g0 + g1 + g2) : tr == 2 ? 0.5 * (g0 - g1 + g2) : g2;
-                        f[((((size_t)hg * MTn + mt) * 2 + ps) * 64 + lane) * 4 + q] = (float)v;
-                    }
-    return f;
-}
-
-// Winograd F(4,3) form of the same conv for the persistent denoiser's WINO == 2 instances (points 0, +-1, +-2, inf): transformed weights
-// U0 = g0 / 4, U1 = -(g0 + g1 + g2) / 6, U2 = -(g0 - g1 + g2) / 6, U3 = g0 / 24 + g1 / 12 + g2 / 6, U4 = g0 / 24 - g1 / 12 + g2 / 6, U5 = g2
-// (formed in double, rounded once) as A fragments of v_mfma_f32_16x16x4_f32 in the kernel's iteration order
-// [K/4 k-steps][M/64 waves][6 transforms][64 lanes][4]: element e at lane l is input channel 4 ks + (l >> 4), output row 64 w + 16 e + (l & 15).
-constexpr int WINO43_PAD_KS = 4;      // k-steps of zero padding behind a layer's array (the weight ring runs a few stages past the end)
-std::vector<float> to_wino43_fragments(const std::vector<float>& p, int K, int M) {
-    const int NWV = M / 64;
-    std::vector<float> f((size_t)(K / 4 + WINO43_PAD_KS) * NWV * 6 * 64 * 4, 0.0f);
-    for (int ks = 0; ks < K / 4; ++ks)
-        for (int w = 0; w < NWV; ++w)
-            for (int tr = 0; tr < 6; ++tr)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 4; ++e) {
-                        const int k = 4 * ks + (lane >> 4), mrow = 64 * w + 16 * e + (lane & 15);
-                        const double g0 = p[((size_t)0 * K + k) * M + mrow], g1 = p[((size_t)1 * K + k) * M + mrow], g2 = p[((size_t)2 * K + k) * M + mrow];
-                        double v;
-                        switch (tr) {
-                            case 0: v = g0 / 4.0; break;
-                            case 1: v = -(g0 + g1 + g2) / 6.0; break;
-                            case 2: v = -(g0 - g1 + g2) / 6.0; break;
-                            case 3: v = g0 / 24.0 + g1 / 12.0 + g2 / 6.0; break;
-                            case 4: v = g0 / 24.0 - g1 / 12.0 + g2 / 6.0; break;
-                            default: v = g2; break;
-                        }
-                        f[((((size_t)ks * NWV + w) * 6 + tr) * 64 + lane) * 4 + e] = (float)v;
-                    }
-    return f;
-}
-
-// Winograd form of a k-tap conv for conv_xlw_kernel (resblock_pair.h: WinoTab<KT>): the transformed weights of every table entry (formed in
-// double, rounded once) as A fragments in the kernel's iteration order [K/16 chunks][entries][2 halves][M/32][64 lanes][4].
-template <int KT>
-std::vector<float> to_wino_iter_fragments_k(const std::vector<float>& p, int K, int M) {
-    using TAB = WinoTab<KT>;
-    std::vector<float> f((size_t)TAB::N * K * M);
-    const int MTn = M / 32;
-    size_t o = 0;
-    for (int c = 0; c < K / 16; ++c)
-        for (int e = 0; e < TAB::N; ++e)
-            for (int h = 0; h < 2; ++h)
-                for (int mt = 0; mt < MTn; ++mt)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j) {
-                            const int k = 16 * c + 8 * h + 2 * j + (lane >> 5), mrow = 32 * mt + (lane & 31), tau = TAB::e[e].tau;
-                            auto g = [&](int tap) -> double { return tap < KT ? (double)p[((size_t)tap * K + k) * M + mrow] : 0.0; };
-                            double v = 0.0;
-                            switch (TAB::e[e].wkind) {
-                                case 0: v = g(tau); break;
-                                case 1: v = 0.5 * (g(tau) + g(tau + 1) + g(tau + 2)); break;
-                                case 2: v = 0.5 * (g(tau) - g(tau + 1) + g(tau + 2)); break;
-                                case 3: v = g(tau + 2); break;
-                                case 4: v = -g(tau); break;
-                                case 5: v = g(tau) + g(tau + 1); break;
-                                case 6: v = g(tau + 1); break;
-                            }
-                            f[o++] = (float)v;
-                        }
-    return f;
-}
-std::vector<float> to_wino_iter_fragments(const std::vector<float>& p, int taps, int K, int M) {
-    if (taps == 3) return to_wino_iter_fragments_k<3>(p, K, M);
-    if (taps == 7) return to_wino_iter_fragments_k<7>(p, K, M);
-    if (taps == 11) return to_wino_iter_fragments_k<11>(p, K, M);
-    return {};
-}
-
-// F(4,3) form of the FFT blocks' k = 9 FFN conv for conv_xres_kernel<.., WQ = true> (conv_xres.hip): three groups of three taps, six transforms each (U0 .. U5 as in
-// to_wino43_fragments), as A fragments of v_mfma_f32_16x16x4_f32 in the kernel's iteration order [K/4 k-steps][M/32 m-tiles][9][64 lanes][4]: vector j of a (k-step,
-// m-tile) holds transforms 2 j and 2 j + 1 (of tap group j / 3) for the m-tile's two 16-row halves — element (pt & 1) * 2 + i at lane l = input channel 4 ks + (l >> 4),
-// output row 32 mt + 16 i + (l & 15).
-std::vector<float> to_wino43_xres_fragments(const std::vector<float>& p, int taps, int K, int M) {
-    if (taps != 9 || K % 4 || M % 32) return {};
-    const int MTn = M / 32;
-    std::vector<float> f((size_t)(K / 4) * MTn * 9 * 256);
-    for (int ks = 0; ks < K / 4; ++ks)
-        for (int mt = 0; mt < MTn; ++mt)
-            for (int pt = 0; pt < 18; ++pt)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int i = 0; i < 2; ++i) {
-                        const int k = 4 * ks + (lane >> 4), mrow = 32 * mt + 16 * i + (lane & 15), tau = 3 * (pt / 6);
-                        const double g0 = p[((size_t)tau * K + k) * M + mrow], g1 = p[((size_t)(tau + 1) * K + k) * M + mrow], g2 = p[((size_t)(tau + 2) * K + k) * M + mrow];
-                        double v;
-                        switch (pt % 6) {
-                            case 0: v = g0 / 4.0; break;
-                            case 1: v = -(g0 + g1 + g2) / 6.0; break;
-                            case 2: v = -(g0 - g1 + g2) / 6.0; break;
-                            case 3: v = g0 / 24.0 + g1 / 12.0 + g2 / 6.0; break;
-                            case 4: v = g0 / 24.0 - g1 / 12.0 + g2 / 6.0; break;
-                            default: v = g2; break;
-                        }
-                        f[((((size_t)ks * MTn + mt) * 9 + pt / 2) * 64 + lane) * 4 + (pt & 1) * 2 + i] = (float)v;
-                    }
-    return f;
-}
-
-// The same conv as three F(2,3) tap groups over output PAIRS (conv_xres.hip, WQ == 2 instances; round 6): per (k-step of four channels, 32-row m-tile, tap group) the four
-// transformed weights U0 = g0, U1 = (g0 + g1 + g2) / 2, U2 = (g0 - g1 + g2) / 2, U3 = g2 (formed in double, rounded once) for the m-tile's two 16-row halves, as two 16-byte
-// vectors per lane: [K/4][M/32][3][2][64 lanes][4], element (tr & 1) * 2 + i of vector tr / 2 at lane l = transform tr, input channel 4 ks + (l >> 4), output row 32 mt + 16 i + (l & 15).
-std::vector<float> to_wino23_xres_fragments(const std::vector<float>& p, int taps, int K, int M) {
-    if (taps != 9 || K % 4 || M % 32) return {};
-    const int MTn = M / 32;
-    std::vector<float> f((size_t)(K / 4) * MTn * 6 * 256);
-    for (int ks = 0; ks < K / 4; ++ks)
-        for (int mt = 0; mt < MTn; ++mt)
-            for (int g = 0; g < 3; ++g)
-                for (int tr = 0; tr < 4; ++tr)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int i = 0; i < 2; ++i) {
-                            const int k = 4 * ks + (lane >> 4), mrow = 32 * mt + 16 * i + (lane & 15), tau = 3 * g;
-                            const double g0 = p[((size_t)tau * K + k) * M + mrow], g1 = p[((size_t)(tau + 1) * K + k) * M + mrow], g2 = p[((size_t)(tau + 2) * K + k) * M + mrow];
-                            const double v = tr == 0 ? g0 : tr == 1 ? 0.5 * (g0 + g1 + g2) : tr == 2 ? 0.5 * (g0 - g1 + g2) : g2;
-                            f[(((((size_t)ks * MTn + mt) * 3 + g) * 2 + tr / 2) * 64 + lane) * 4 + (tr & 1) * 2 + i] = (float)v;
-                        }
-    return f;
-}
-
-// F(4,3) form of a k-tap, dilation-1 conv for conv_xlq_kernel (conv_xlq.hip: QTab<KT>): per k-step of four input channels the transformed weights of
-// every group of three taps (U0 = g0/4, U1 = -(g0+g1+g2)/6, U2 = -(g0-g1+g2)/6, U3 = g0/24 + g1/12 + g2/6, U4 = g0/24 - g1/12 + g2/6, U5 = g2; a tap beyond the
-// kernel is zero) and, for k = 7, of the seventh tap on its own (g, g/2, g/2, g) — formed in double, rounded once — as A fragments of v_mfma_f32_16x16x4_f32 in
-// the kernel's iteration order [K/4 k-steps][M/64 waves][points][64 lanes][4]: element i at lane l = input channel 4 ks + (l >> 4), output row 64 w + 16 i + (l & 15).
-std::vector<float> to_wino43_iter_fragments(const std::vector<float>& p, int taps, int K, int M) {
-    if ((taps != 3 && taps != 5 && taps != 7 && taps != 11) || K % 4 || M % 64) return {};
-    const int ngrp = taps == 3 ? 1 : taps <= 7 ? 2 : 4, npt = ngrp * 6 + (taps == 7 ? 4 : 0), NWV = M / 64;
-    std::vector<float> f((size_t)(K / 4) * NWV * npt * 256);
-    for (int ks = 0; ks < K / 4; ++ks)
-        for (int w = 0; w < NWV; ++w)
-            for (int pt = 0; pt < npt; ++pt)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int i = 0; i < 4; ++i) {
-                        const int k = 4 * ks + (lane >> 4), mrow = 64 * w + 16 * i + (lane & 15);
-                        auto g = [&](int tap) -> double { return tap < taps ? (double)p[((size_t)tap * K + k) * M + mrow] : 0.0; };
-                        double v;
-                        if (pt < ngrp * 6) {
-                            const int tau = 3 * (pt / 6);
-                            const double g0 = g(tau), g1 = g(tau + 1), g2 = g(tau + 2);
-                            switch (pt % 6) {
-                                case 0: v = g0 / 4.0; break;
-                                case 1: v = -(g0 + g1 + g2) / 6.0; break;
-                                case 2: v = -(g0 - g1 + g2) / 6.0; break;
-                                case 3: v = g0 / 24.0 + g1 / 12.0 + g2 / 6.0; break;
-                                case 4: v = g0 / 24.0 - g1 / 12.0 + g2 / 6.0; break;
-                                default: v = g2; break;
-                            }
-                        } else {
-                            const int q = pt - ngrp * 6;
-                            v = (q == 1 || q == 2) ? 0.5 * g(6) : g(6);
-                        }
-                        f[((((size_t)ks * NWV + w) * npt + pt) * 64 + lane) * 4 + i] = (float)v;
-                    }
-    return f;
-}
-
-// The same fragments in the ITERATION order of the fused ResBlock pair kernels (resblock_pair.hip): the K loop walks
-// (16-channel chunk, tap, 8-channel half), so [K/16][taps][2][M/32][64 lanes][4] makes the weight stream one linear walk.
-std::vector<float> to_fragment_iter_order(const std::vector<float>& p, int taps, int K, int M) {
-    std::vector<float> f((size_t)taps * K * M);
-    const int MTn = M / 32;
-    size_t o = 0;
-    for (int c = 0; c < K / 16; ++c)
-        for (int tap = 0; tap < taps; ++tap)
-            for (int h = 0; h < 2; ++h)
-                for (int mt = 0; mt < MTn; ++mt)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j)
-                            f[o++] = p[((size_t)tap * K + 16 * c + 8 * h + 2 * j + (lane >> 5)) * M + 32 * mt + (lane & 31)];
-    return f;
-}
-
-inline unsigned short host_cvt16(float f, int mode) {   // mode 1 = bf16 (round to nearest even), 2 = fp16
-    if (mode == 1) {
-        unsigned u;
-        memcpy(&u, &f, 4);
-        return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    }
-    const _Float16 h = (_Float16)f;
-    unsigned short r;
-    memcpy(&r, &h, 2);
-    return r;
-}
-
-// k-major packed weights [taps][K][M] -> 16-bit MFMA A-fragment order for v_mfma_f32_32x32x16_{bf16,f16}:
-// [taps][K/16][M/32][64 lanes][8]: element (lane, j) = P[tap][16g + 8 (lane >> 5) + j][32 mt + (lane & 31)].
-std::vector<unsigned short> to_fragment16(const std::vector<float>& p, int taps, int K, int M, int mode) {
-    std::vector<unsigned short> f((size_t)taps * K * M);
-    const int G = K / 16, MTn = M / 32;
-    for (int tap = 0; tap < taps; ++tap)
-        for (int g = 0; g < G; ++g)
-            for (int mt = 0; mt < MTn; ++mt)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j)
-                        f[((((size_t)tap * G + g) * MTn + mt) * 64 + lane) * 8 + j] =
-                            host_cvt16(p[((size_t)tap * K + 16 * g + 8 * (lane >> 5) + j) * M + 32 * mt + (lane & 31)], mode);
-    return f;
-}
-
-// The same fragments in the ITERATION order of conv_mfma16.hip's deep-ring variant: its K loop walks (32-channel chunk, tap,
-// k-group of the chunk), so [K/32][taps][2][M/32][64 lanes][8] makes the weight stream one linear walk (K % 32 == 0).
-std::vector<unsigned short> to_fragment16_iter(const std::vector<float>& p, int taps, int K, int M, int mode) {
-    std::vector<unsigned short> f((size_t)taps * K * M);
-    const int MTn = M / 32;
-    size_t o = 0;
-    for (int c = 0; c < K / 32; ++c)
-        for (int tap = 0; tap < taps; ++tap)
-            for (int h = 0; h < 2; ++h)
-                for (int mt = 0; mt < MTn; ++mt)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j)
-                            f[o++] = host_cvt16(p[((size_t)tap * K + 32 * c + 16 * h + 8 * (lane >> 5) + j) * M + 32 * mt + (lane & 31)], mode);
-    return f;
-}
-
-// fp16x3 operands: every weight as hi = fp16(w) and lo = fp16(w - hi); the lo fragment set follows the hi set
-std::vector<unsigned short> to_fragment16_split(const std::vector<float>& p, int taps, int K, int M) {
-    std::vector<float> hi(p.size()), lo(p.size());
-    for (size_t i = 0; i < p.size(); ++i) {
-        const _Float16 h = (_Float16)p[i];
-        hi[i] = (float)h;
-        lo[i] = p[i] - (float)h;
-    }
-    std::vector<unsigned short> f = to_fragment16(hi, taps, K, M, 2);
-    const std::vector<unsigned short> fl = to_fragment16(lo, taps, K, M, 2);
-    f.insert(f.end(), fl.begin(), fl.end());
-    return f;
-}
-
-// nn.Linear weight [N][K] -> transposed [K][N] (dense_small operand / X operand of a GEMM)
-std::vector<float> transpose2d(const float* w, int N, int K) {
-    std::vector<float> t((size_t)K * N);
-    for (int n = 0; n < N; ++n)
-        for (int k = 0; k < K; ++k) t[(size_t)k * N + n] = w[(size_t)n * K + k];
-    return t;
-}
-
-std::vector<float> omega_table(int C) {
-    // SinusoidalPositionalEmbedding.get_embedding (model/blocks.py:50-54): exp(arange(half) * -ln(1e4)/(half-1)) in fp32
-    const int half = C / 2;
-    const float e = (float)(log(10000.0) / (half - 1));
-    std::vector<float> w(half);
-    for (int j = 0; j < half; ++j) w[j] = (float)exp((double)((float)j * -e));
-    return w;
-}
-
-// Sinusoid table rows 0..rows-1 (row 0 = padding = zeros): fp32 argument p*w_j, sine/cosine in f64 rounded to
-// fp32 — the same recipe the kernels use on the fly beyond the table.
-constexpr int PE_ROWS = 4096;
-std::vector<float> pe_table(int C, int rows) {
-    const std::vector<float> w = omega_table(C);
-    const int half = C / 2;
-    std::vector<float> t((size_t)rows * C, 0.f);
-    for (int p = 1; p < rows; ++p)
-        for (int c = 0; c < C; ++c) {
-            const float arg = (float)p * w[c < half ? c : c - half];
-            t[(size_t)p * C + c] = c < half ? (float)sin((double)arg) : (float)cos((double)arg);
-        }
-    return t;
-}
+namespace {
 
 ConvArgs conv_args(const PackedConv& w, const float* X, int Tin, int ldx, long x_bs, float* Y, int ldy, long y_bs, int N) {
     ConvArgs a;
@@ -662,468 +268,6 @@ int persist_blocks() {          // workgroups that are certainly co-resident: on
     static int n = [] { int dev = 0, v = 0; (void)hipGetDevice(&dev);
                         (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v; }();
     return n;
-}
-
-struct EncLayer {
-    float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
-    PackedConv qk, qkv, wo, ffn1, ffn2;     // qkv: the whole in_proj_weight as one [3H][H] contraction (fused attention path)
-    float* ffn1_f = nullptr;   // ffn1 as MFMA A fragments in iteration order (conv_xres.hip)
-    float* ffn1_q = nullptr;   // ffn1 (k = 9, 256 input channels) as F(4,3) fragments (conv_xres.hip, WQ == 1 instances: to_wino43_xres_fragments), else null
-    float* ffn1_p = nullptr;   // ... as F(2,3) fragments (WQ == 2 instances: to_wino23_xres_fragments), else null
-    float* qkv_f = nullptr;    // the same for the in-projection and the out-projection (round 2: LayerNorm + projection in one launch)
-    float* wo_f = nullptr;
-    float* ffn2_f = nullptr;   // the FFN linear as A fragments in iteration order: conv_xres.hip's FFN fusion
-    void* ffn1_f16[2] = {nullptr, nullptr};   // bf16 / fp16 fragment-order copies of the two FFN contractions (conv_mfma16.hip; the opt-in "text16")
-    void* ffn2_f16[2] = {nullptr, nullptr};
-    void* qkv_f16[2] = {nullptr, nullptr};    // ... and of the in- / out-projection of the self-attention
-    void* wo_f16[2] = {nullptr, nullptr};
-    float* wvT;  // [256 c][256 d]
-};
-struct Predictor {
-    std::vector<PackedConv> convs;
-    std::vector<float*> convs_f;     // 256 -> 256 convs as MFMA A fragments in iteration order (conv_xl_kernel), else null
-    std::vector<void*> convs_f16[2]; // bf16 / fp16 fragment-order copies (conv_mfma16.hip; the opt-in "text16"), else null
-    std::vector<float*> convs_q;     // k = 5 convs into 256 rows: F(4,3) transformed weights (conv_k5q.hip: to_wino43_iter_fragments), else null
-    std::vector<float*> ln_g, ln_b;
-    float *lin_w = nullptr, *lin_b = nullptr, *alpha = nullptr;
-    int odim = 0;
-};
-struct ResLayer {
-    PackedConv cond, conv3, outp;
-    float *w3f = nullptr, *wof = nullptr;   // fragment-order copies for the fused kernel
-    float* w3w = nullptr;                   // Winograd F(2,3) transformed conv weights as A fragments (persistent denoiser, 8-wave WINO instances)
-    float* w3w43 = nullptr;                 // Winograd F(4,3) transformed conv weights (8-wave WINO == 2 instances: to_wino43_fragments)
-    float* b3f = nullptr;                   // conv_layer bias in the fused kernel's row order
-    void *w3f16[3] = {nullptr, nullptr, nullptr}, *wof16[3] = {nullptr, nullptr, nullptr};   // bf16 / fp16 / fp16x3 (hi | lo) fragment-order copies
-};
-
-}  // namespace
-
-struct cmtts_model {
-    cmtts_config cfg;
-    std::map<std::string, HostTensor> host;
-    bool finalized = false;
-    int precision = 0;     // operand precision of the residual-block contractions: 0 fp32, 1 bf16, 2 fp16
-    int text16 = 0;        // 16-bit models (precision 1 / 2): the FFN contractions of the FFT blocks with 16-bit operands too (opt-in: the text side feeds the integer stages — durations, pitch buckets, lengths — which then depend on the precision mode; cmtts_model_set_option)
-    int winograd = 1;                       // fp32 persistent denoiser: Winograd k = 3 conv (cmtts_model_set_option "winograd"): 1 = F(4,3) (~8e-6 on the mel against the direct form),
-                                            // 2 = F(2,3) (~4e-6), 0 = direct
-    int batch_invariant = 0;                // fp32, winograd = 1: the per-layer residual blocks in the persistent stack's F(4,3) form (cmtts_model_set_option "batch_invariant")
-    int ffn2_split = 1;    // FFT blocks: the FFN linear as 8 partial GEMMs over K segments + one reduction (another fp32 summation order than one launch: a property of the model handle, cmtts_model_set_option)
-    cmtts_variance_controls vc = {1.f, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    cmtts_control_tables ct = {nullptr, nullptr, nullptr, 0};      // per-phoneme control tables [B][ld] (cmtts_set_control_tables); a table replaces the scalar of its control
-    Allocs al;
-    float *embed = nullptr, *omega_h = nullptr, *omega_cwt = nullptr, *omega_res = nullptr;
-    float *pe_h = nullptr, *pe_cwt = nullptr;   // sinusoid tables [PE_ROWS][C]
-    std::vector<EncLayer> enc;
-    float *encln_g = nullptr, *encln_b = nullptr;
-    // FastspeechDecoder (model/modules.py:154-165): optional, present when the state dict holds "decoder.*"
-    std::vector<EncLayer> dec;
-    float *decln_g = nullptr, *decln_b = nullptr, *dec_alpha = nullptr;
-    float *spk_wt = nullptr, *spk_b = nullptr, *spk_table = nullptr;
-    Predictor dur, energy, cwt;
-    PackedConv cwt_in;
-    float* cwt_in_f = nullptr;     // the same as MFMA A fragments in iteration order (conv_xres.hip)
-    float *energy_bins = nullptr, *energy_emb = nullptr, *pitch_emb = nullptr;
-    float *st0_wt = nullptr, *st0_b = nullptr, *st2_wt = nullptr, *st2_b = nullptr, *st4_wt = nullptr, *st4_b = nullptr;
-    PackedConv in_proj, skip_proj, out_proj;
-    float* in_proj_f = nullptr;   // input projection as MFMA A fragments (inproj.hip)
-    float *skip_f = nullptr, *outp_f = nullptr;   // skip / output projection in fragment order (persistent kernel's tail)
-    PackedConv cond_all;   // the 20 conditioner_projections stacked: [256][NL*256] (+ stacked bias)
-    float* cond_all_f = nullptr;   // the same in MFMA A-fragment order (cond_gemm.hip)
-    // factored conditioner projections (cond_factored below): P2[r][i] = sum_k Wc[r][k] * pitch_embed[i][k] + bias[r], [NL*C][pitch_bins],
-    // computed once at cmtts_finalize with cond_gemm_kernel itself; a zero bias vector for the phoneme-level factor
-    float* cond_p2 = nullptr;
-    float* cond_p2t = nullptr;             // [NL][pitch_bins][C]: cond_p2 with the channels contiguous (PersistArgs.p2t)
-    float* cond_zero_bias = nullptr;
-    void* cond_all_f16[3] = {nullptr, nullptr, nullptr};   // bf16 / fp16 / fp16x3 (hi | lo) fragment-order copies (cond_gemm16.hip)
-    float *mlp0_wt = nullptr, *mlp2_wt = nullptr, *dproj_wt = nullptr, *sproj_wt = nullptr;
-    std::vector<ResLayer> res;
-    // Step-embedding cache (round 2): the DiffusionEmbedding -> MLP -> 20 stacked diffusion projections of a timestep depend
-    // on nothing but the timestep, and the consistency sampler evaluates every batch at the same few sigmas: the row
-    // [NL * C] of each rescaled timestep seen by cmtts_sample is kept on the device (first use computes and copies it; an
-    // entry is used once the event recorded behind that copy has completed, whatever stream asks).
-    struct StepRow { float t; float* row; hipEvent_t ready; };
-    std::vector<StepRow> step_rows;
-};
-
-struct cmtts_vocoder {
-    std::map<std::string, HostTensor> host;
-    bool finalized = false;
-    Allocs al;
-    PackedConv conv_pre;
-    PackedConv ups[4];
-    float* ups_f[4] = {nullptr, nullptr, nullptr, nullptr};   // two-tap stacked-phase weights as iteration-order fragments (convT_xl_kernel)
-    void* ups_f16[4][3] = {};                                  // the same as bf16 / fp16 / fp16x3 (hi | lo) fragments (convT_xl16_kernel)
-    int up_rate[4] = {8, 8, 2, 2};
-    int up_kernel[4] = {16, 16, 4, 4};
-    int rb_kernel[3] = {3, 7, 11};
-    int rb_dil[3] = {1, 3, 5};
-    PackedConv c1[12][3], c2[12][3];
-    void *c1f[12][3][3] = {}, *c2f[12][3][3] = {};   // bf16 / fp16 / fp16x3 (hi | lo) fragment-order copies of the ResBlock convs
-    float *c1f32[12][3] = {}, *c2f32[12][3] = {};    // fp32 fragments in iteration order (resblock_pair.hip: pair kernels at C <= 64, conv_xl above)
-    float *c1q32[12][3] = {}, *c2q32[12][3] = {};    // F(4,3) fragments of the dilation-1 convs (conv_xlq_kernel; c1q32 only for the first pair of a ResBlock), else null
-    float *c1w32[12][3] = {}, *c2w32[12][3] = {};    // Winograd-transformed fragments of the C >= 128 stages (conv_xlw_kernel), else null
-    int winograd = 1;                                 // fp32 generator: ResBlock convs of the C >= 128 stages in their Winograd form (cmtts_vocoder_set_option "winograd")
-    int batch_invariant = 0;                          // fp32 generator: every launch-size gate takes its large-launch branch (cmtts_vocoder_set_option "batch_invariant")
-    int precision = 0;                               // 0 fp32, 1 bf16, 2 fp16 operands in the ResBlock convs
-    int ups16 = 1;                                    // 16-bit modes: upsampler operands in 16 bits as well (cmtts_vocoder_set_option "ups16"; 0 = fp32 upsamplers, different numerics)
-    float *post_w = nullptr, *post_b = nullptr;
-    int post_cin = 32, post_k = 7;
-};
-
-namespace {
-
-int set_tensor(std::map<std::string, HostTensor>& host, const char* name, const float* data, const int64_t* shape, int ndim) {
-    if (!name || !data || ndim < 0 || ndim > 4) return fail(CMTTS_E_INVALID, "set_tensor: bad argument");
-    HostTensor t;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) {
-        if (shape[i] <= 0) return fail(CMTTS_E_INVALID, std::string("set_tensor: bad shape for ") + name);
-        t.shape.push_back(shape[i]);
-        n *= (size_t)shape[i];
-    }
-    t.data.assign(data, data + n);
-    host[name] = std::move(t);
-    return 0;
-}
-
-struct Getter {
-    const std::map<std::string, HostTensor>& host;
-    std::string missing;
-    const HostTensor* get(const std::string& name, std::initializer_list<int64_t> shape) {
-        auto it = host.find(name);
-        if (it == host.end()) {
-            if (missing.empty()) missing = "missing tensor " + name;
-            return nullptr;
-        }
-        if (it->second.shape != std::vector<int64_t>(shape)) {
-            if (missing.empty()) missing = "wrong shape for tensor " + name;
-            return nullptr;
-        }
-        return &it->second;
-    }
-};
-
-int finalize_model(cmtts_model* m) {
-    const cmtts_config& c = m->cfg;
-    if (c.hidden != 256 || c.res_channels != 256 || c.pred_filter != 256)
-        return fail(CMTTS_E_UNSUPPORTED, "kernels are specialised for hidden = residual_channels = filter_size = 256");
-    if (c.hidden % c.enc_heads) return fail(CMTTS_E_INVALID, "hidden not divisible by heads (model/blocks.py:209)");
-    const int H = c.hidden, C = c.res_channels;
-    Getter g{m->host, ""};
-    Allocs& al = m->al;
-#define GET(var, name, ...)                                     \
-    const HostTensor* var = g.get(name, {__VA_ARGS__});          \
-    if (!var) return fail(CMTTS_E_INVALID, g.missing)
-#define UP(dst, t) CHK(al.upload((t)->data, &(dst)))
-
-    CHK(al.upload(omega_table(H), &m->omega_h));
-    CHK(al.upload(omega_table(c.cwt_hidden), &m->omega_cwt));
-    CHK(al.upload(omega_table(C), &m->omega_res));
-    CHK(al.upload(pe_table(H, PE_ROWS), &m->pe_h));
-    CHK(al.upload(pe_table(c.cwt_hidden, PE_ROWS), &m->pe_cwt));
-
-    const std::string enc = "duration_pitch_energy_net.text_encoder.";
-    GET(emb, enc + "embed_tokens.weight", c.n_symbols, H);
-    UP(m->embed, emb);
-    // one EncSALayer (model/blocks.py:560-618): shared by the text encoder and the optional FastspeechDecoder
-    auto load_fft_layer = [&](const std::string& p, EncLayer& L) -> int {
-        GET(l1g, p + "layer_norm1.weight", H); GET(l1b, p + "layer_norm1.bias", H);
-        GET(l2g, p + "layer_norm2.weight", H); GET(l2b, p + "layer_norm2.bias", H);
-        UP(L.ln1_g, l1g); UP(L.ln1_b, l1b); UP(L.ln2_g, l2g); UP(L.ln2_b, l2b);
-        GET(inw, p + "self_attn.in_proj_weight", 3 * H, H);
-        HostTensor qk; qk.shape = {2 * H, H, 1};
-        qk.data.assign(inw->data.begin(), inw->data.begin() + (size_t)2 * H * H);
-        CHK(pack_conv(al, qk, nullptr, nullptr, &L.qk));
-        HostTensor qkv = *inw; qkv.shape = {3 * H, H, 1};
-        {
-            std::vector<float> hp;
-            CHK(pack_conv(al, qkv, nullptr, nullptr, &L.qkv, &hp));
-            if (H % 32 == 0 && L.qkv.ld == L.qkv.cout) CHK(al.upload(to_fragment_iter_order(hp, 1, H, 3 * H), &L.qkv_f));
-            if (H % 32 == 0 && L.qkv.ld == L.qkv.cout)
-                for (int mode = 1; mode <= 2; ++mode) {
-                    const std::vector<unsigned short> f16 = to_fragment16(hp, 1, H, 3 * H, mode);
-                    CHK(al.upload_bytes(f16.data(), f16.size() * 2, &L.qkv_f16[mode - 1]));
-                }
-        }
-        CHK(al.upload(transpose2d(inw->data.data() + (size_t)2 * H * H, H, H), &L.wvT));
-        GET(ow, p + "self_attn.out_proj.weight", H, H);
-        HostTensor ow3 = *ow; ow3.shape = {H, H, 1};
-        {
-            std::vector<float> hp;
-            CHK(pack_conv(al, ow3, nullptr, nullptr, &L.wo, &hp));
-            if (H % 32 == 0 && L.wo.ld == L.wo.cout) CHK(al.upload(to_fragment_iter_order(hp, 1, H, H), &L.wo_f));
-            if (H % 32 == 0 && L.wo.ld == L.wo.cout)
-                for (int mode = 1; mode <= 2; ++mode) {
-                    const std::vector<unsigned short> f16 = to_fragment16(hp, 1, H, H, mode);
-                    CHK(al.upload_bytes(f16.data(), f16.size() * 2, &L.wo_f16[mode - 1]));
-                }
-        }
-        GET(f1w, p + "ffn.ffn_1.weight", 4 * H, H, c.ffn_kernel); GET(f1b, p + "ffn.ffn_1.bias", 4 * H);
-        {
-            std::vector<float> hp;
-            CHK(pack_conv(al, *f1w, f1b, nullptr, &L.ffn1, &hp));
-            if (L.ffn1.cin % 32 == 0 && L.ffn1.cout % 32 == 0 && L.ffn1.ld == L.ffn1.cout)
-                CHK(al.upload(to_fragment_iter_order(hp, L.ffn1.taps, L.ffn1.cin, L.ffn1.cout), &L.ffn1_f));
-            if (L.ffn1.taps == 9 && L.ffn1.cin == 256 && L.ffn1.cout % 128 == 0 && L.ffn1.ld == L.ffn1.cout)
-            {
-                CHK(al.upload(to_wino43_xres_fragments(hp, L.ffn1.taps, L.ffn1.cin, L.ffn1.cout), &L.ffn1_q));
-                CHK(al.upload(to_wino23_xres_fragments(hp, L.ffn1.taps, L.ffn1.cin, L.ffn1.cout), &L.ffn1_p));
-            }
-            if (L.ffn1.cin % 32 == 0 && L.ffn1.cout % 32 == 0 && L.ffn1.ld == L.ffn1.cout)
-                for (int mode = 1; mode <= 2; ++mode) {
-                    const std::vector<unsigned short> f16 = to_fragment16(hp, L.ffn1.taps, L.ffn1.cin, L.ffn1.cout, mode);
-                    CHK(al.upload_bytes(f16.data(), f16.size() * 2, &L.ffn1_f16[mode - 1]));
-                }
-        }
-        GET(f2w, p + "ffn.ffn_2.weight", H, 4 * H); GET(f2b, p + "ffn.ffn_2.bias", H);
-        HostTensor f2 = *f2w; f2.shape = {H, 4 * H, 1};
-        {
-            std::vector<float> hp;
-            CHK(pack_conv(al, f2, f2b, nullptr, &L.ffn2, &hp));
-            if (H == 256 && L.ffn2.cin % 128 == 0 && L.ffn2.ld == L.ffn2.cout) CHK(al.upload(to_fragment_iter_order(hp, 1, L.ffn2.cin, H), &L.ffn2_f));
-            if (L.ffn2.cin % 32 == 0 && H % 32 == 0 && L.ffn2.ld == L.ffn2.cout)
-                for (int mode = 1; mode <= 2; ++mode) {
-                    const std::vector<unsigned short> f16 = to_fragment16(hp, 1, L.ffn2.cin, H, mode);
-                    CHK(al.upload_bytes(f16.data(), f16.size() * 2, &L.ffn2_f16[mode - 1]));
-                }
-        }
-        return 0;
-    };
-    m->enc.resize(c.enc_layers);
-    for (int i = 0; i < c.enc_layers; ++i) CHK(load_fft_layer(enc + "layers." + std::to_string(i) + ".op.", m->enc[i]));
-    GET(eg, enc + "layer_norm.weight", H); GET(eb, enc + "layer_norm.bias", H);
-    UP(m->encln_g, eg); UP(m->encln_b, eb);
-    {   // optional FastspeechDecoder: as many layers as the state dict holds under "decoder.layers.N.op."
-        int nd = 0;
-        while (m->host.count("decoder.layers." + std::to_string(nd) + ".op.layer_norm1.weight")) ++nd;
-        if (nd > 0) {
-            m->dec.resize(nd);
-            for (int i = 0; i < nd; ++i) CHK(load_fft_layer("decoder.layers." + std::to_string(i) + ".op.", m->dec[i]));
-            GET(dg, "decoder.layer_norm.weight", H); GET(db, "decoder.layer_norm.bias", H);
-            UP(m->decln_g, dg); UP(m->decln_b, db);
-            GET(da, "decoder.pos_embed_alpha", 1);
-            UP(m->dec_alpha, da);
-        }
-    }
-
-    if (c.multi_speaker && c.n_speaker > 0) {   // speaker_embedder "none": nn.Embedding(n_speaker, hidden) (model/cmtts.py:26-38)
-        GET(sw, "duration_pitch_energy_net.speaker_emb.weight", c.n_speaker, H);
-        UP(m->spk_table, sw);
-    } else if (c.multi_speaker) {
-        GET(sw, "duration_pitch_energy_net.speaker_emb.weight", H, c.external_speaker_dim);
-        GET(sb, "duration_pitch_energy_net.speaker_emb.bias", H);
-        CHK(al.upload(transpose2d(sw->data.data(), H, c.external_speaker_dim), &m->spk_wt));
-        UP(m->spk_b, sb);
-    }
-
-    const std::string va = "duration_pitch_energy_net.variance_adaptor.";
-    auto load_pred = [&](Predictor& P, const std::string& p, int idim, int n_layers, int k, int odim, bool alpha) -> int {
-        P.convs.resize(n_layers); P.ln_g.resize(n_layers); P.ln_b.resize(n_layers); P.odim = odim;
-        for (int li = 0; li < n_layers; ++li) {
-            const int cin = li == 0 ? idim : c.pred_filter;
-            const std::string q = p + "conv." + std::to_string(li);
-            GET(w, q + ".1.weight", c.pred_filter, cin, k); GET(b, q + ".1.bias", c.pred_filter);
-            {
-                std::vector<float> hp;
-                CHK(pack_conv(al, *w, b, nullptr, &P.convs[li], &hp));
-                P.convs_f.resize(n_layers, nullptr);
-                if ((cin == 256 || (cin == 128 && k == 5)) && c.pred_filter == 256 && P.convs[li].ld == 256)
-                    CHK(al.upload(to_fragment_iter_order(hp, k, cin, c.pred_filter), &P.convs_f[li]));
-                P.convs_q.resize(n_layers, nullptr);
-                if (k == 5 && (cin == 256 || cin == 128) && c.pred_filter == 256 && P.convs[li].ld == 256) {
-                    const std::vector<float> wq = to_wino43_iter_fragments(hp, k, cin, c.pred_filter);
-                    if (!wq.empty()) CHK(al.upload(wq, &P.convs_q[li]));
-                }
-                for (int mode = 1; mode <= 2; ++mode) {
-                    P.convs_f16[mode - 1].resize(n_layers, nullptr);
-                    if (cin % 32 == 0 && c.pred_filter % 32 == 0 && P.convs[li].ld == c.pred_filter) {
-                        const std::vector<unsigned short> f16 = to_fragment16(hp, k, cin, c.pred_filter, mode);
-                        CHK(al.upload_bytes(f16.data(), f16.size() * 2, &P.convs_f16[mode - 1][li]));
-                    }
-                }
-            }
-            GET(lg, q + ".3.weight", c.pred_filter); GET(lb, q + ".3.bias", c.pred_filter);
-            UP(P.ln_g[li], lg); UP(P.ln_b[li], lb);
-        }
-        GET(lw, p + "linear.weight", odim, c.pred_filter); GET(lb2, p + "linear.bias", odim);
-        UP(P.lin_w, lw); UP(P.lin_b, lb2);
-        if (alpha) { GET(a, p + "pos_embed_alpha", 1); UP(P.alpha, a); }
-        return 0;
-    };
-    CHK(load_pred(m->dur, va + "duration_predictor.", H, c.dur_layers, c.dur_kernel, 1, false));
-    CHK(load_pred(m->energy, va + "energy_predictor.", H, c.pred_layers, c.pred_kernel, 1, true));
-    const int cwt_out = c.use_uv ? 11 : 10;
-    CHK(load_pred(m->cwt, va + "cwt_predictor.1.", c.cwt_hidden, c.pred_layers, c.pred_kernel, cwt_out, true));
-    {
-        GET(w, va + "cwt_predictor.0.weight", c.cwt_hidden, H); GET(b, va + "cwt_predictor.0.bias", c.cwt_hidden);
-        HostTensor w3 = *w; w3.shape = {c.cwt_hidden, H, 1};
-        {
-            std::vector<float> hp;
-            CHK(pack_conv(al, w3, b, nullptr, &m->cwt_in, &hp));
-            if (H % 32 == 0 && c.cwt_hidden % 32 == 0 && m->cwt_in.ld == c.cwt_hidden)
-                CHK(al.upload(to_fragment_iter_order(hp, 1, H, c.cwt_hidden), &m->cwt_in_f));
-        }
-        GET(bins, va + "energy_bins", c.energy_bins - 1); UP(m->energy_bins, bins);
-        GET(ee, va + "energy_embedding.weight", c.energy_bins, H); UP(m->energy_emb, ee);
-        GET(pe, va + "pitch_embed.weight", c.pitch_bins, H); UP(m->pitch_emb, pe);
-        GET(s0w, va + "cwt_stats_layers.0.weight", c.cwt_hidden, H); GET(s0b, va + "cwt_stats_layers.0.bias", c.cwt_hidden);
-        GET(s2w, va + "cwt_stats_layers.2.weight", c.cwt_hidden, c.cwt_hidden); GET(s2b, va + "cwt_stats_layers.2.bias", c.cwt_hidden);
-        GET(s4w, va + "cwt_stats_layers.4.weight", 2, c.cwt_hidden); GET(s4b, va + "cwt_stats_layers.4.bias", 2);
-        CHK(al.upload(transpose2d(s0w->data.data(), c.cwt_hidden, H), &m->st0_wt)); UP(m->st0_b, s0b);
-        CHK(al.upload(transpose2d(s2w->data.data(), c.cwt_hidden, c.cwt_hidden), &m->st2_wt)); UP(m->st2_b, s2b);
-        CHK(al.upload(transpose2d(s4w->data.data(), 2, c.cwt_hidden), &m->st4_wt)); UP(m->st4_b, s4b);
-    }
-
-    // ---- denoiser
-    {
-        GET(w, "net.input_projection.0.conv.weight", C, c.n_mels, 1); GET(b, "net.input_projection.0.conv.bias", C);
-        {
-            std::vector<float> hp;
-            CHK(pack_conv(al, *w, b, nullptr, &m->in_proj, &hp));
-            if (c.n_mels % 8 == 0 && C % 32 == 0 && m->in_proj.ld == C) CHK(al.upload(to_fragment_order(hp, 1, c.n_mels, C), &m->in_proj_f));
-        }
-        GET(m0, "net.mlp.0.linear.weight", 4 * C, C); GET(m2, "net.mlp.2.linear.weight", C, 4 * C);
-        CHK(al.upload(transpose2d(m0->data.data(), 4 * C, C), &m->mlp0_wt));
-        CHK(al.upload(transpose2d(m2->data.data(), C, 4 * C), &m->mlp2_wt));
-    }
-    const int NL = c.res_layers;
-    m->res.resize(NL);
-    std::vector<float> dproj((size_t)C * NL * C), sproj;
-    if (c.multi_speaker) sproj.resize((size_t)H * NL * C);
-    // gate permutation: packed 64-row group g = [rows g*32.. of the sigmoid half | rows C + g*32.. of the tanh half]
-    std::vector<int> perm(2 * C);
-    for (int gidx = 0; gidx < C / 32; ++gidx)
-        for (int i = 0; i < 32; ++i) {
-            perm[gidx * 64 + i] = gidx * 32 + i;
-            perm[gidx * 64 + 32 + i] = C + gidx * 32 + i;
-        }
-    for (int l = 0; l < NL; ++l) {
-        const std::string p = "net.residual_layers." + std::to_string(l) + ".";
-        GET(w3, p + "conv_layer.conv.weight", 2 * C, C, 3); GET(b3, p + "conv_layer.conv.bias", 2 * C);
-        std::vector<float> hp;
-        CHK(pack_conv(al, *w3, b3, &perm, &m->res[l].conv3));
-        {   // fused kernel: every 32-row tile = [16 sigmoid rows | 16 tanh rows] of the same 16 channels
-            std::vector<int> perm16(2 * C);
-            for (int gidx = 0; gidx < C / 16; ++gidx)
-                for (int i = 0; i < 16; ++i) {
-                    perm16[gidx * 32 + i] = gidx * 16 + i;
-                    perm16[gidx * 32 + 16 + i] = C + gidx * 16 + i;
-                }
-            PackedConv tmp;
-            Allocs scratch;                                   // device copy of the k-major form is not needed
-            CHK(pack_conv(scratch, *w3, b3, &perm16, &tmp, &hp));
-            CHK(al.upload(to_fragment_order(hp, 3, C, 2 * C), &m->res[l].w3f));
-            if (C == 256) CHK(al.upload(to_wino_fragments(hp, C, 2 * C), &m->res[l].w3w));
-            if (C == 256) CHK(al.upload(to_wino43_fragments(hp, C, 2 * C), &m->res[l].w3w43));
-            for (int mode = 1; mode <= 2; ++mode) {
-                const std::vector<unsigned short> f16 = to_fragment16(hp, 3, C, 2 * C, mode);
-                CHK(al.upload_bytes(f16.data(), f16.size() * 2, &m->res[l].w3f16[mode - 1]));
-            }
-            {
-                const std::vector<unsigned short> fs = to_fragment16_split(hp, 3, C, 2 * C);
-                CHK(al.upload_bytes(fs.data(), fs.size() * 2, &m->res[l].w3f16[2]));
-            }
-            std::vector<float> bperm(2 * C);
-            for (int r = 0; r < 2 * C; ++r) bperm[r] = b3->data[perm16[r]];
-            CHK(al.upload(bperm, &m->res[l].b3f));
-            scratch.release();
-        }
-        GET(wc, p + "conditioner_projection.conv.weight", C, H, 1); GET(bc, p + "conditioner_projection.conv.bias", C);
-        CHK(pack_conv(al, *wc, bc, nullptr, &m->res[l].cond));
-        GET(wo, p + "output_projection.conv.weight", 2 * C, C, 1); GET(bo, p + "output_projection.conv.bias", 2 * C);
-        CHK(pack_conv(al, *wo, bo, nullptr, &m->res[l].outp, &hp));
-        CHK(al.upload(to_fragment_order(hp, 1, C, 2 * C), &m->res[l].wof));
-        for (int mode = 1; mode <= 2; ++mode) {
-            const std::vector<unsigned short> f16 = to_fragment16(hp, 1, C, 2 * C, mode);
-            CHK(al.upload_bytes(f16.data(), f16.size() * 2, &m->res[l].wof16[mode - 1]));
-        }
-        {
-            const std::vector<unsigned short> fs = to_fragment16_split(hp, 1, C, 2 * C);
-            CHK(al.upload_bytes(fs.data(), fs.size() * 2, &m->res[l].wof16[2]));
-        }
-        GET(wd, p + "diffusion_projection.linear.weight", C, C);
-        for (int n = 0; n < C; ++n)
-            for (int k = 0; k < C; ++k) dproj[(size_t)k * NL * C + l * C + n] = wd->data[(size_t)n * C + k];
-        if (c.multi_speaker) {
-            GET(ws, p + "speaker_projection.linear.weight", C, H);
-            for (int n = 0; n < C; ++n)
-                for (int k = 0; k < H; ++k) sproj[(size_t)k * NL * C + l * C + n] = ws->data[(size_t)n * H + k];
-        }
-    }
-    {   // stacked conditioner projections (one GEMM for all layers; cond does not depend on the step)
-        HostTensor W, Bv;
-        W.shape = {(int64_t)NL * C, H, 1};
-        W.data.resize((size_t)NL * C * H);
-        Bv.shape = {(int64_t)NL * C};
-        Bv.data.resize((size_t)NL * C);
-        for (int l = 0; l < NL; ++l) {
-            const std::string p = "net.residual_layers." + std::to_string(l) + ".";
-            const HostTensor& wc = m->host.at(p + "conditioner_projection.conv.weight");
-            const HostTensor& bc = m->host.at(p + "conditioner_projection.conv.bias");
-            std::copy(wc.data.begin(), wc.data.end(), W.data.begin() + (size_t)l * C * H);
-            std::copy(bc.data.begin(), bc.data.end(), Bv.data.begin() + (size_t)l * C);
-        }
-        std::vector<float> hp;
-        CHK(pack_conv(al, W, &Bv, nullptr, &m->cond_all, &hp));
-        if (H % 8 == 0 && (NL * C) % 32 == 0 && m->cond_all.ld == NL * C)
-            CHK(al.upload(to_fragment_order(hp, 1, H, NL * C), &m->cond_all_f));
-        if (H % 16 == 0 && (NL * C) % 32 == 0 && m->cond_all.ld == NL * C)
-            for (int mode = 1; mode <= 2; ++mode) {
-                const std::vector<unsigned short> f16 = to_fragment16(hp, 1, H, NL * C, mode);
-                CHK(al.upload_bytes(f16.data(), f16.size() * 2, &m->cond_all_f16[mode - 1]));
-            }
-        if (H % 16 == 0 && (NL * C) % 32 == 0 && m->cond_all.ld == NL * C) {
-            const std::vector<unsigned short> fs = to_fragment16_split(hp, 1, H, NL * C);
-            CHK(al.upload_bytes(fs.data(), fs.size() * 2, &m->cond_all_f16[2]));
-        }
-    }
-    CHK(al.upload(dproj, &m->dproj_wt));
-    if (c.multi_speaker) CHK(al.upload(sproj, &m->sproj_wt));
-    {
-        GET(w, "net.skip_projection.conv.weight", C, C, 1); GET(b, "net.skip_projection.conv.bias", C);
-        std::vector<float> hp;
-        CHK(pack_conv(al, *w, b, nullptr, &m->skip_proj, &hp));
-        if (C % 32 == 0 && m->skip_proj.ld == C) CHK(al.upload(to_fragment_order(hp, 1, C, C), &m->skip_f));
-        GET(w2, "net.output_projection.conv.weight", c.n_mels, C, 1); GET(b2, "net.output_projection.conv.bias", c.n_mels);
-        CHK(pack_conv(al, *w2, b2, nullptr, &m->out_proj, &hp));
-        {   // rows padded to a multiple of 32 with zeros for the MFMA tiles of the fused tail
-            const int ld = m->out_proj.ld, Mp = round_up(c.n_mels, 32);
-            std::vector<float> padded((size_t)C * Mp, 0.f);
-            for (int k = 0; k < C; ++k)
-                for (int n = 0; n < c.n_mels; ++n) padded[(size_t)k * Mp + n] = hp[(size_t)k * ld + n];
-            CHK(al.upload(to_fragment_order(padded, 1, C, Mp), &m->outp_f));
-        }
-    }
-    if (m->cond_all_f && (NL * C) % 512 == 0) {
-        // the pitch-table factor of the conditioner projections: the stacked GEMM on pitch_embed^T [H][pitch_bins] (one "utterance" of
-        // pitch_bins "frames"), bias included
-        GET(pe, va + "pitch_embed.weight", c.pitch_bins, H);
-        float* peT = nullptr;
-        void* p2 = nullptr;
-        CHK(al.upload(transpose2d(pe->data.data(), c.pitch_bins, H), &peT));
-        CHK(al.upload(std::vector<float>((size_t)NL * C, 0.f), &m->cond_zero_bias));
-        HIPCHK(hipMalloc(&p2, (size_t)NL * C * c.pitch_bins * sizeof(float) + 256));
-        al.ptrs.push_back(p2);
-        CondGemmArgs ga;
-        memset(&ga, 0, sizeof(ga));
-        ga.X = peT; ga.Wf = m->cond_all_f; ga.bias = m->cond_all.bias; ga.Y = (float*)p2;
-        ga.B = 1; ga.T = c.pitch_bins; ga.M = NL * C; ga.K = H; ga.force = 1; ga.row_split = NL * C / 512;
-        if (cmtts_launch_cond_gemm(&ga, nullptr) == 0) {
-            void* p2t = nullptr;
-            HIPCHK(hipMalloc(&p2t, (size_t)NL * C * c.pitch_bins * sizeof(float) + 256));
-            al.ptrs.push_back(p2t);
-            k_transpose((const float*)p2, (float*)p2t, NL, C, c.pitch_bins, nullptr);      // [NL][C][bins] -> [NL][bins][C]
-            HIPCHK(hipStreamSynchronize(nullptr));
-            m->cond_p2 = (float*)p2;
-            m->cond_p2t = (float*)p2t;
-        }
-    }
-#undef GET
-#undef UP
-    m->host.clear();
-    m->finalized = true;
-    return 0;
 }
 
 // ---------------------------------------------------------------- workspaces
@@ -2665,77 +1809,9 @@ int cmtts_vocoder_set_tensor(cmtts_vocoder* v, const char* name, const float* ho
 }
 int cmtts_vocoder_finalize(cmtts_vocoder* v) {
     if (!v || v->finalized) return fail(CMTTS_E_INVALID, "cmtts_vocoder_finalize: null or finalized");
-    Getter g{v->host, ""};
-    Allocs& al = v->al;
-#define GETV(var, name, ...)                                     \
-    const HostTensor* var = g.get(name, {__VA_ARGS__});           \
-    if (!var) { al.release(); return fail(CMTTS_E_INVALID, g.missing); }
-    GETV(pw, "conv_pre.weight", 512, 80, 7); GETV(pb, "conv_pre.bias", 512);
-    CHK(pack_conv(al, *pw, pb, nullptr, &v->conv_pre));
-    int ch = 512;
-    for (int i = 0; i < 4; ++i) {
-        const int co = ch / 2;
-        GETV(uw, "ups." + std::to_string(i) + ".weight", ch, co, v->up_kernel[i]);
-        GETV(ub, "ups." + std::to_string(i) + ".bias", co);
-        {
-            std::vector<float> tt;
-            CHK(pack_conv_transpose(al, *uw, *ub, v->up_rate[i], &v->ups[i], &tt));
-            const int mrows = v->up_rate[i] * co;
-            if (!tt.empty() && ch % 16 == 0 && mrows % 32 == 0) {
-                CHK(al.upload(to_fragment_iter_order(tt, 2, ch, mrows), &v->ups_f[i]));
-                for (int mode = 1; mode <= 2; ++mode) {
-                    const std::vector<unsigned short> f16 = to_fragment16(tt, 2, ch, mrows, mode);
-                    CHK(al.upload_bytes(f16.data(), f16.size() * 2, &v->ups_f16[i][mode - 1]));
-                }
-                const std::vector<unsigned short> fs = to_fragment16_split(tt, 2, ch, mrows);
-                CHK(al.upload_bytes(fs.data(), fs.size() * 2, &v->ups_f16[i][2]));
-            }
-        }
-        for (int j = 0; j < 3; ++j) {
-            const int r = i * 3 + j;
-            for (int mi = 0; mi < 3; ++mi) {
-                const std::string p = "resblocks." + std::to_string(r);
-                GETV(w1, p + ".convs1." + std::to_string(mi) + ".weight", co, co, v->rb_kernel[j]);
-                GETV(b1, p + ".convs1." + std::to_string(mi) + ".bias", co);
-                GETV(w2, p + ".convs2." + std::to_string(mi) + ".weight", co, co, v->rb_kernel[j]);
-                GETV(b2, p + ".convs2." + std::to_string(mi) + ".bias", co);
-                std::vector<float> hp;
-                CHK(pack_conv(al, *w1, b1, nullptr, &v->c1[r][mi], &hp));
-                CHK(al.upload(to_fragment_iter_order(hp, v->rb_kernel[j], co, co), &v->c1f32[r][mi]));
-                if (co >= 128 || (co == 64 && v->rb_kernel[j] >= 7)) { const std::vector<float> wf = to_wino_iter_fragments(hp, v->rb_kernel[j], co, co); if (!wf.empty()) CHK(al.upload(wf, &v->c1w32[r][mi])); }
-                if (co >= 64) { const std::vector<float> wf = to_wino43_iter_fragments(hp, v->rb_kernel[j], co, co); if (!wf.empty()) CHK(al.upload(wf, &v->c1q32[r][mi])); }     // (C = 64, k = 3: the fused F(4,3) pair, conv_xlq_pair.hip)
-                for (int mode = 1; mode <= 2; ++mode) {
-                    const std::vector<unsigned short> f16 = to_fragment16(hp, v->rb_kernel[j], co, co, mode);
-                    CHK(al.upload_bytes(f16.data(), f16.size() * 2, &v->c1f[r][mi][mode - 1]));
-                }
-                {
-                    const std::vector<unsigned short> fs = to_fragment16_split(hp, v->rb_kernel[j], co, co);
-                    CHK(al.upload_bytes(fs.data(), fs.size() * 2, &v->c1f[r][mi][2]));
-                }
-                CHK(pack_conv(al, *w2, b2, nullptr, &v->c2[r][mi], &hp));
-                CHK(al.upload(to_fragment_iter_order(hp, v->rb_kernel[j], co, co), &v->c2f32[r][mi]));
-                if (co >= 128 || (co == 64 && v->rb_kernel[j] >= 7)) { const std::vector<float> wf = to_wino_iter_fragments(hp, v->rb_kernel[j], co, co); if (!wf.empty()) CHK(al.upload(wf, &v->c2w32[r][mi])); }
-                if (co >= 64) { const std::vector<float> wf = to_wino43_iter_fragments(hp, v->rb_kernel[j], co, co); if (!wf.empty()) CHK(al.upload(wf, &v->c2q32[r][mi])); }
-                for (int mode = 1; mode <= 2; ++mode) {
-                    const std::vector<unsigned short> f16 = to_fragment16(hp, v->rb_kernel[j], co, co, mode);
-                    CHK(al.upload_bytes(f16.data(), f16.size() * 2, &v->c2f[r][mi][mode - 1]));
-                }
-                {
-                    const std::vector<unsigned short> fs = to_fragment16_split(hp, v->rb_kernel[j], co, co);
-                    CHK(al.upload_bytes(fs.data(), fs.size() * 2, &v->c2f[r][mi][2]));
-                }
-            }
-        }
-        ch = co;
-    }
-    GETV(qw, "conv_post.weight", 1, ch, 7); GETV(qb, "conv_post.bias", 1);
-    CHK(al.upload(qw->data, &v->post_w));
-    CHK(al.upload(qb->data, &v->post_b));
-    v->post_cin = ch;
-#undef GETV
-    v->host.clear();
-    v->finalized = true;
-    return 0;
+    const int r = finalize_vocoder(v);
+    if (r != 0) v->al.release();
+    return r;
 }
 void cmtts_vocoder_destroy(cmtts_vocoder* v) {
     if (!v) return;

@@ -5,7 +5,7 @@
 // The products are conv_xlq.hip's (HiFi-GAN, round 5): five taps = two groups of three with a zero sixth tap; a group at tap offset o reads
 // d0..d5 = X[4q + o .. 4q + o + 5] of the quad's input row (column j of the staged tile = frame t0 - 2 + j) and forms
 //   V0 = 4 d0 - 5 d2 + d4, V1 = (d4 - 4 d2) + (d3 - 4 d1), V2 = (d4 - 4 d2) - (d3 - 4 d1), V3 = (d4 - d2) + 2 (d3 - d1), V4 = (d4 - d2) - 2 (d3 - d1),
-//   V5 = 4 d1 - 5 d3 + d5;   M_p += U_p V_p  (U = cmtts_api.hip: to_wino43_iter_fragments, formed in double, rounded once);
+//   V5 = 4 d1 - 5 d3 + d5;   M_p += U_p V_p  (U = weight_pack.cpp: to_wino43_iter_fragments, formed in double, rounded once);
 //   y0 = M0 + (M1 + M2) + (M3 + M4), y1 = (M1 - M2) + 2 (M3 - M4), y2 = (M1 + M2) + 4 (M3 + M4), y3 = (M1 - M2) + 8 (M3 - M4) + M5
 // — 12 products per quad instead of 20.  One n-tile of v_mfma_f32_16x16x4_f32 = one transform of the tile's 16 quads = 64 output frames; lane
 // (q = l & 15, k = l >> 4) owns quad q in input channel 4 ks + k, so all six transforms of a quad are in-lane.  A wave owns 64 output rows (four

@@ -17,7 +17,7 @@
 // One n-tile of v_mfma_f32_16x16x4_f32 = one transform of the tile's 16 quads = 64 output columns: lane (q = l & 15, k = l >> 4) owns quad q in
 // channel 4 ks + k, so the six transforms of a quad sit in one lane and both transforms are in-lane.  A wave owns 64 output rows (four 16-row
 // m-tiles x six transforms = 24 accumulators of 4 registers); a workgroup = C / 64 waves, all C rows of a 64-column tile; the activated tile
-// [C][64 + k - 1] in LDS in natural column order (two aligned LDS reads per group and k-step).  Weights (cmtts_api.hip: to_wino43_iter_fragments,
+// [C][64 + k - 1] in LDS in natural column order (two aligned LDS reads per group and k-step).  Weights (weight_pack.cpp: to_wino43_iter_fragments,
 // formed in double, rounded once) stream L2 -> VGPR in iteration order [k-step][wave][point][64 lanes][4 m-tiles] through a buffer descriptor
 // (lane offset constant, step offset scalar) and a register ring; no barrier in the K loop.
 // NOT bitwise the direct form (fp32 Winograd; measured on the waveform next to the F(2,3) form in tests/test_gpu_parity.py); restated in

@@ -35,14 +35,14 @@ constexpr int RING = 4;
 // WQ (round 5): the k = 9 FFN conv of the fused launch as three F(4,3) tap groups over output QUADS (points 0, +-1, +-2, inf: 18 products per quad instead of 36) —
 // denoiser_persist.hip's WINO == 2 products on v_mfma_f32_16x16x4_f32: lane (q = l & 15, k = l >> 4) owns quad q of an n-tile of 16 quads in channel 4 ks + k; a wave's
 // 32 rows = two 16-row m-tiles x six transforms x NTQ n-tiles (96-column tiles: 24 quads in two n-tiles, the last eight quad lanes idle; 32-column tiles: eight quads in
-// one).  wfrag = cmtts_api.hip: to_wino43_xres_fragments ([K/4][M/32][9][64 lanes][4]: element (pt & 1) * 2 + i of vector pt / 2 = transform pt, m-tile i).  Every
+// one).  wfrag = weight_pack.cpp: to_wino43_xres_fragments ([K/4][M/32][9][64 lanes][4]: element (pt & 1) * 2 + i of vector pt / 2 = transform pt, m-tile i).  Every
 // output element sees the same products in the same order whatever the tile width, so the 96- and 32-column instances agree bit for bit; against the direct form the
 // difference is fp32 rounding (tests/test_gpu_parity.py).  Everything around the K loop — staging, LayerNorm prologue, GELU, the FFN linear's partial product — is unchanged.
 // WQ == 2 (round 6, the default for fp32 models): the same three tap groups as F(2,3) over output PAIRS (points 0, +-1, inf: m0 = (d0 - d2) g0, m1 = (d1 + d2) (g0 + g1 + g2) / 2,
 // m2 = (d2 - d1) (g0 - g1 + g2) / 2, m3 = (d1 - d3) g2; y(2p) = m0 + m1 + m2, y(2p + 1) = m1 - m2 - m3).  A 96-column tile is 48 pairs = THREE full n-tiles of 16 pair lanes where it
 // is 24 quads = one and a half n-tiles of quad lanes: 4 transforms x 3 n-tiles = the 6 x 2 MFMAs of the F(4,3) form per (k-step, tap group, m-tile) — the same matrix work — with 3
 // instead of 16 VALU operations per transformed n-tile, four transformed weight sets instead of six, and F(2,3)'s smaller rounding error (an output depends on its own taps only); a
-// 32-column tile is ONE full n-tile of pairs (F(4,3): six transforms on half an n-tile of quads: 1.5 x the MFMAs).  wfrag = cmtts_api.hip: to_wino23_xres_fragments
+// 32-column tile is ONE full n-tile of pairs (F(4,3): six transforms on half an n-tile of quads: 1.5 x the MFMAs).  wfrag = weight_pack.cpp: to_wino23_xres_fragments
 // ([K/4][M/32][3 groups][2][64 lanes][4]: element (tr & 1) * 2 + i of vector tr / 2 = transform tr, m-tile half i).
 template <bool LN, int NT, int WQ = 0>
 __global__ __launch_bounds__(256, NT == 1 ? XRES_OCC1 : 1) void conv_xres_kernel(const ConvArgs a, const float* __restrict__ wfrag, long long* dbg) {

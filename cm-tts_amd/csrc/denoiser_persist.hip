@@ -92,7 +92,7 @@ __device__ __forceinline__ void store_granule(unsigned long long* g, unsigned ta
 // products per quad instead of twelve (98 k pipe cycles per layer).  With d0..d5 = u(4q-1 .. 4q+4): V0 = 4 d0 - 5 d2 + d4,
 // V1 = (d4 - 4 d2) + (d3 - 4 d1), V2 = (d4 - 4 d2) - (d3 - 4 d1), V3 = (d4 - d2) + 2 (d3 - d1), V4 = (d4 - d2) - 2 (d3 - d1),
 // V5 = 4 d1 - 5 d3 + d5; m_p = U_p V_p with U0 = g0/4, U1 = -(g0+g1+g2)/6, U2 = -(g0-g1+g2)/6, U3 = g0/24 + g1/12 + g2/6,
-// U4 = g0/24 - g1/12 + g2/6, U5 = g2 (cmtts_api.hip: to_wino43_fragments); y0 = m0 + (m1+m2) + (m3+m4), y1 = (m1-m2) + 2 (m3-m4),
+// U4 = g0/24 - g1/12 + g2/6, U5 = g2 (weight_pack.cpp: to_wino43_fragments); y0 = m0 + (m1+m2) + (m3+m4), y1 = (m1-m2) + 2 (m3-m4),
 // y2 = (m1+m2) + 4 (m3+m4), y3 = (m1-m2) + 8 (m3-m4) + m5.  One n-tile of v_mfma_f32_16x16x4_f32 = one transform of the tile's 16 quads
 // (all six transforms of a quad in the same lane), a wave carries 4 sixteen-row m-tiles x 6 transforms = 24 accumulators of 4 registers;
 // u in natural frame order.  State, barriers, halo protocol, FACT, RAGGED, tail: as WINO == 1.  Restated in oracle/winograd_ref.py
@@ -100,7 +100,7 @@ __device__ __forceinline__ void store_granule(unsigned long long* g, unsigned ta
 // WINO == 1 (round 4): the gated k = 3 conv as a Winograd F(2,3) convolution along the frame axis — per PAIR of output frames four products
 // instead of six: m0 = (d0 - d2) g0, m1 = (d1 + d2) (g0 + g1 + g2)/2, m2 = (d2 - d1) (g0 - g1 + g2)/2, m3 = (d1 - d3) g2,
 // y(2p) = m0 + m1 + m2, y(2p+1) = m1 - m2 - m3 with d0..d3 = u(2p-1 .. 2p+2).  Each m_i is its own K = 256 contraction over the
-// channels (transformed weights W3f = [64 half-groups][16 m-tiles][2][64 lanes][4], packed by cmtts_api.hip: to_wino_fragments), so a
+// channels (transformed weights W3f = [64 half-groups][16 m-tiles][2][64 lanes][4], packed by weight_pack.cpp: to_wino_fragments), so a
 // wave carries 2 m-tiles x 4 transforms = 8 accumulators over ONE 32-pair n-tile and the conv costs 2/3 of the direct form's MFMAs
 // (131 k instead of 197 k pipe cycles per layer).  u lives in LDS split by frame parity (odd frames at row offset (f + 1) / 2,
 // even frames at 33 + f / 2) so that the four d_i of a pair are unit-stride reads; the residual stream x makes room in the register
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
         constexpr int WR = WINO_RING, NH = C / 4;
         f32x4 Aw[WINO == 1 ? WR : 1][MT][2];
         // WINO == 2, F(4,3): a stage = one k-step of FOUR channels of all six transforms for this wave's four 16-row m-tiles: 6 x 16 bytes per lane,
-        // element e of fragment p = transform p, m-tile e (cmtts_api.hip: to_wino43_fragments)
+        // element e of fragment p = transform p, m-tile e (weight_pack.cpp: to_wino43_fragments)
         constexpr int WR4 = WINO43_RING, NS4 = C / 4;
         f32x4 A4[WINO == 2 ? WR4 : 1][6];
         // (buffer loads: the layer's array as a descriptor, the lane's fragment offset in a VGPR that never changes, the k-step's offset
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
                 dst[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + p * 1024, ks * (NW * 6 * 64 * 16), 0));
         };
         // (uniform base + 32-bit lane offset: the saddr form, no per-step VALU address arithmetic; the ring reads up to WR - 1 half-groups past
-        //  the layer's last one — the packer pads every layer's array by that much, cmtts_api.hip: to_wino_fragments)
+        //  the layer's last one — the packer pads every layer's array by that much, weight_pack.cpp: to_wino_fragments)
         auto load_aw = [&](f32x4 (&dst)[MT][2], const float* wfrag, int hg) {
             const char* base = reinterpret_cast<const char*>(wfrag) + (size_t)hg * ((2 * C / 32) * 2 * 64 * 16);
 #pragma unroll

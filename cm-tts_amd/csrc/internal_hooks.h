@@ -15,6 +15,8 @@
 // with voc_wino's launch-size rule, 2 always; <= 1e-6 on the waveform between the arms).  The switches are process-wide and unsynchronised.  Exported from libcmtts_hip.so so that ctypes can reach it
 // (cmtts_amd/_lib.py: internal_set).
 #pragma once
+#include <stddef.h>
+#include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -37,6 +39,12 @@ int cmtts_internal_mel_window_gather(const float* mel_ct, int B, int T, const in
 // Test hook: the raw Philox4x32-10 blocks of the seeded noise (noise_philox.hip), before Box-Muller: bits uint32
 // [n_draws][B][T][ceil(M / 4)][4] for the arguments of cmtts_noise_fill (seeds: device int64 [B]).
 int cmtts_internal_noise_bits(const int64_t* seeds, int B, int T, int M, int first_draw, int n_draws, int64_t t0, uint32_t* bits, void* stream);
+// Test hook: one of the host-side weight packers (weight_pack.h) on HOST memory; never touches the GPU.  layout = the packer's name without "to_"
+// (fragment_order, fragment_iter_order, fragment16, fragment16_iter, fragment16_split, wino_fragments, wino43_fragments, wino_iter_fragments,
+// wino43_iter_fragments, wino43_xres_fragments, wino23_xres_fragments); kmajor [taps][K][M] floats; mode 1 = bf16 / 2 = fp16 for fragment16 and
+// fragment16_iter, ignored elsewhere.  *need = the size of the packed stream in bytes, padding included; out == NULL only queries it.  An unknown
+// layout, a (taps, K, M) the packer does not cover or out_bytes < *need returns CMTTS_E_INVALID.
+int cmtts_internal_pack_weights(const char* layout, const float* kmajor, int taps, int K, int M, int mode, void* out, size_t out_bytes, size_t* need);
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,7 @@ struct ConvXlArgs {
 };
 
 // ---- Winograd form of a k-tap (dilated) Conv1d for the fp32 X-resident kernels (round 4; conv_xlw_kernel in resblock_pair.hip, weights packed by
-// cmtts_api.hip: to_wino_iter_fragments).  Outputs are computed in PAIRS (t, t + dil); with X(m) = act(x)[t + (m - (k-1)/2) dil] the k taps split
+// weight_pack.cpp: to_wino_iter_fragments).  Outputs are computed in PAIRS (t, t + dil); with X(m) = act(x)[t + (m - (k-1)/2) dil] the k taps split
 // into groups of three consecutive taps done as F(2,3) (4 products per pair instead of 6), a leftover pair of taps as F(2,2) (3 instead of
 // 4) and a leftover single tap directly (2):  k = 3: 4 products per pair instead of 6, k = 7: 10 instead of 14, k = 11: 15 instead of 22.
 // Every product is one entry of this table: accumulator M_acc += W_kind(tau) * (X(a) + sgn X(b))   (sgn = 0: X(a) alone), and

@@ -1,0 +1,26 @@
+// Host-only weight packers: k-major conv weights [taps][K][M] (P[tap][input channel k][output row]) -> the MFMA A-fragment streams the
+// kernels read, each in its kernel's iteration order.  Plain C++17: no HIP header, no device code (import.hip uploads the results;
+// internal_hooks.h: cmtts_internal_pack_weights exposes every packer to the CPU tests).  Each layout is specified at its definition in
+// weight_pack.cpp.
+#pragma once
+#include <vector>
+
+constexpr int WINO_PAD_HG = 4;        // to_wino_fragments: half-groups of zero padding behind a layer's array: the kernel's weight ring runs a few stages past the end
+constexpr int WINO43_PAD_KS = 4;      // to_wino43_fragments: k-steps of zero padding behind a layer's array (the weight ring runs a few stages past the end)
+
+unsigned short host_cvt16(float f, int mode);   // mode 1 = bf16 (round to nearest even), 2 = fp16
+
+// fp32, v_mfma_f32_32x32x2_f32 (K % 8 == 0 / K % 16 == 0 for the iteration orders, M % 32 == 0)
+std::vector<float> to_fragment_order(const std::vector<float>& p, int taps, int K, int M);
+std::vector<float> to_fragment_iter_order(const std::vector<float>& p, int taps, int K, int M);
+std::vector<float> to_wino_fragments(const std::vector<float>& p, int K, int M);
+std::vector<float> to_wino_iter_fragments(const std::vector<float>& p, int taps, int K, int M);         // {} unless taps = 3 / 7 / 11
+// fp32, v_mfma_f32_16x16x4_f32 (K % 4 == 0; M % 64 == 0, the xres forms M % 32 == 0)
+std::vector<float> to_wino43_fragments(const std::vector<float>& p, int K, int M);
+std::vector<float> to_wino43_iter_fragments(const std::vector<float>& p, int taps, int K, int M);       // {} unless taps = 3 / 5 / 7 / 11
+std::vector<float> to_wino43_xres_fragments(const std::vector<float>& p, int taps, int K, int M);       // {} unless taps = 9
+std::vector<float> to_wino23_xres_fragments(const std::vector<float>& p, int taps, int K, int M);       // {} unless taps = 9
+// 16-bit, v_mfma_f32_32x32x16_{bf16,f16} (K % 16 == 0 / K % 32 == 0 for the iteration order, M % 32 == 0)
+std::vector<unsigned short> to_fragment16(const std::vector<float>& p, int taps, int K, int M, int mode);
+std::vector<unsigned short> to_fragment16_iter(const std::vector<float>& p, int taps, int K, int M, int mode);
+std::vector<unsigned short> to_fragment16_split(const std::vector<float>& p, int taps, int K, int M);

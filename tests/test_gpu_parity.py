@@ -2407,7 +2407,7 @@ def test_errors_are_loud():
 
 
 def _pack_wino43(w):
-    """w [Cout][Cin][k] (torch layout) -> conv_xlq_kernel's weight stream (cmtts_api.hip: to_wino43_iter_fragments; conv_xlq.hip: QTab<k>):
+    """w [Cout][Cin][k] (torch layout) -> conv_xlq_kernel's weight stream (weight_pack.cpp: to_wino43_iter_fragments; conv_xlq.hip: QTab<k>):
     [Cin/4 k-steps][Cout/64 waves][points][64 lanes][4], element i at lane l = input channel 4 ks + (l >> 4), output row 64 w + 16 i + (l & 15)."""
     from oracle import winograd_ref as W
     cout, cin, k = w.shape

@@ -77,3 +77,59 @@ def test_f43_tap_groups_equal_direct_conv(k):
     e_dir = np.abs(W.conv1d_direct(x, w, 1) - ref64).max()
     e_q = np.abs(W.conv1d_f43_taps(x, w) - ref64).max()
     assert e_q < 16 * e_dir + 1e-6, (k, e_q, e_dir)
+
+
+# ---- the same algebra on the weights the C++ packers emit (cm-tts_amd/csrc/weight_pack.cpp through csrc/internal_hooks.h: cmtts_internal_pack_weights): the fragment
+# stream is decoded back to U[transform][Cout][Cin] with the inverse index map and replaces the restated transform.  The streams hold float32, so the float64
+# bounds above can only hold when the transforms are exact in float32: the weights are integer multiples of 24 / 128 (|w| <= 1.5) — every sum of three, every
+# division by 2, 4, 6, 12 and 24 of such values is an integer multiple of 2^-7 far below 2^24 — and the packer's single rounding then loses nothing.
+def _exact_weights(rs, cout, cin, k):
+    return rs.randint(-8, 9, size=(cout, cin, k)) * (24.0 / 128.0)
+
+
+def _decoded(layout, w):
+    from cmtts_amd import _lib
+    cout, cin, k = w.shape
+    p = np.ascontiguousarray(w.transpose(2, 1, 0), np.float32)          # k-major [taps][Cin][Cout]
+    assert np.array_equal(p.astype(np.float64), w.transpose(2, 1, 0))
+    raw = _lib.internal_pack_weights(layout, p)
+    assert raw is not None, (layout, w.shape)
+    return W.unpack_weights(layout, raw.view(np.float32), k, cin, cout)
+
+
+@pytest.mark.parametrize("k,dil", [(3, 1), (3, 3), (3, 5), (7, 1), (7, 3), (7, 5), (9, 1), (11, 1), (11, 3), (11, 5)])
+def test_winograd_table_on_packed_weights_equals_direct_conv(k, dil):
+    rs = np.random.RandomState(100 * k + dil)
+    w = _exact_weights(rs, 32, 16, k)
+    U = _decoded("wino23_xres_fragments" if k == 9 else "wino_iter_fragments", w)
+    assert len(U) == len(W.WINO_TAB[k])
+    for T in (1, 2, 59, 60, 61, 64, 137):
+        x = rs.standard_normal((16, T))
+        ref = W.conv1d_direct(x, w, dil)
+        got = W.conv1d_winograd(x, w, dil, U=U)
+        assert got.shape == ref.shape
+        assert np.abs(got - ref).max() < 1e-12 * max(1.0, np.abs(ref).max()), (k, dil, T)
+
+
+def test_denoiser_f23_stream_holds_the_table_weights():
+    """to_wino_fragments (denoiser_persist.hip, WINO instances) carries the same four transforms as the k = 3 table, in its own fragment order."""
+    w = _exact_weights(np.random.RandomState(5), 32, 16, 3)
+    assert np.array_equal(_decoded("wino_fragments", w), _decoded("wino_iter_fragments", w))
+
+
+@pytest.mark.parametrize("T", [1, 3, 4, 63, 64, 65, 130])
+def test_f43_on_packed_weights_equals_direct_conv(T):
+    rs = np.random.RandomState(T)
+    x = rs.standard_normal((16, T))
+    w = _exact_weights(rs, 64, 16, 3)
+    assert np.abs(W.conv1d_f43(x, w, U=_decoded("wino43_fragments", w)) - W.conv1d_direct(x, w, 1)).max() < 1e-12
+
+
+@pytest.mark.parametrize("k", [3, 5, 7, 9, 11])
+def test_f43_tap_groups_on_packed_weights_equal_direct_conv(k):
+    rs = np.random.RandomState(k)
+    w = _exact_weights(rs, 64, 16, k)
+    U = _decoded("wino43_xres_fragments" if k == 9 else "wino43_iter_fragments", w)
+    for T in (1, 2, 5, 63, 64, 66, 131):
+        x = rs.standard_normal((16, T))
+        assert np.abs(W.conv1d_f43_taps(x, w, U=U) - W.conv1d_direct(x, w, 1)).max() < 1e-11, (k, T)
