@@ -34,6 +34,11 @@ class ControlTablesStruct(C.Structure):
     _fields_ = [("d", C.c_void_p), ("e", C.c_void_p), ("p", C.c_void_p), ("ld", C.c_int)]
 
 
+class DurationTargetsStruct(C.Structure):
+    """struct cmtts_duration_targets (include/cmtts_hip.h): int32 device pointers as void*."""
+    _fields_ = [("seg", C.c_void_p), ("target", C.c_void_p), ("unmet", C.c_void_p), ("ld", C.c_int), ("n_seg", C.c_int)]
+
+
 class SampleGroupStruct(C.Structure):
     """struct cmtts_sample_group (include/cmtts_hip.h)."""
     _fields_ = [("noise", C.c_void_p), ("cond_ct", C.c_void_p), ("speaker_emb", C.c_void_p), ("B", C.c_int32), ("T", C.c_int32),
@@ -62,6 +67,8 @@ SIGNATURES = {
     "cmtts_text_forward_ragged": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_set_variance_controls": (_i, [_vp, C.POINTER(VarianceControlsStruct)]),
     "cmtts_set_control_tables": (_i, [_vp, C.POINTER(ControlTablesStruct)]),
+    "cmtts_set_duration_targets": (_i, [_vp, C.POINTER(DurationTargetsStruct)]),
+    "cmtts_phoneme_marks": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "cmtts_frame_workspace_bytes": (_sz, [_vp, _i, _i]),
     "cmtts_frame_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_frame_forward_sub": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -283,6 +290,20 @@ def internal_noise_bits(seeds, B, T, M, first_draw, n_draws, t0, bits, stream):
         _noise_bits = C.CDLL(LIB_PATH).cmtts_internal_noise_bits
         _noise_bits.restype, _noise_bits.argtypes = _i, [_vp, _i, _i, _i, _i, _i, _i64, _vp, _vp]
     return _noise_bits(seeds, int(B), int(T), int(M), int(first_draw), int(n_draws), int(t0), bits, stream)
+
+
+_duration_fit = None
+
+
+def internal_duration_fit(d_rounded, cum, mel_len, src_lens, seg, target, unmet, B, L, n_seg, stream):
+    """csrc/internal_hooks.h: cmtts_internal_duration_fit — the fit kernel alone on the caller's device buffers (tools/ and tests only;
+    pointers as integers or None).  Returns the status."""
+    global _duration_fit
+    load()
+    if _duration_fit is None:
+        _duration_fit = C.CDLL(LIB_PATH).cmtts_internal_duration_fit
+        _duration_fit.restype, _duration_fit.argtypes = _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]
+    return _duration_fit(d_rounded, cum, mel_len, src_lens, seg, target, unmet, int(B), int(L), int(n_seg), stream)
 
 
 _pack_weights = None

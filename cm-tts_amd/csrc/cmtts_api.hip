@@ -1086,6 +1086,15 @@ int cmtts_text_forward_ragged(cmtts_model* m, const int64_t* texts, const int64_
         return fail(CMTTS_E_INVALID, "cmtts_text_forward: a duration table replaces d_control, which must then be 1");
     if (ct.e && m->vc.e_control != 1.0f)
         return fail(CMTTS_E_INVALID, "cmtts_text_forward: an energy table replaces e_control, which must then be 1");
+    const cmtts_duration_targets& dt = m->dt;
+    if (dt.target) {
+        if (dt.ld != L)
+            return fail(CMTTS_E_INVALID, "cmtts_text_forward: the duration targets' row pitch ld must equal L (cmtts_set_duration_targets)");
+        if (m->vc.d_target)
+            return fail(CMTTS_E_INVALID, "cmtts_text_forward: duration targets beside a teacher-forced d_target: absolute durations leave nothing to fit");
+        if (k_duration_fit_lds_bytes(L) > 64 * 1024)
+            return fail(CMTTS_E_INVALID, "cmtts_text_forward: duration targets take L up to 4096");
+    }
     TextWs w = carve_text(c, B, L, text_ws);
     if (text_ws_bytes < w.bytes) return fail(CMTTS_E_WORKSPACE, "text workspace too small");
     hipStream_t s = (hipStream_t)stream;
@@ -1130,6 +1139,9 @@ int cmtts_text_forward_ragged(cmtts_model* m, const int64_t* texts, const int64_
     } else {
         k_durations(log_d, d_control, d_rounded, w.cum, mel_len, B, L, s);
     }
+    // duration targets: the integers of each segment apportioned to its frame count; rewrites d_rounded, cum and mel_len, which is all that
+    // anything downstream reads.  Without targets nothing is launched here.
+    if (dt.target) k_duration_fit(d_rounded, w.cum, mel_len, src_lens, dt.seg, dt.target, dt.unmet, B, L, dt.n_seg, s);
     // the pitch table is read on the frame side, which may run on another rank: its rows become part of the text-side state
     if (ct.p) HIPCHK(hipMemcpyAsync(w.pctl, ct.p, (size_t)B * L * 4, hipMemcpyDeviceToDevice, s));
     if (enc_out_ct && !c.multi_speaker)
@@ -2374,6 +2386,16 @@ int cmtts_internal_mel_window_gather(const float* mel_ct, int B, int T, const in
                                                                                                               : fail(CMTTS_E_HIP, "gather launch failed");
 }
 
+int cmtts_internal_duration_fit(float* d_rounded, int* cum, int64_t* mel_len, const int64_t* src_lens, const int32_t* seg, const int32_t* target,
+                                int32_t* unmet, int B, int L, int n_seg, void* stream) {
+    if (!d_rounded || !cum || !mel_len || !src_lens || !target || B <= 0 || L <= 0 || n_seg < 1 || (!seg && n_seg != 1) ||
+        k_duration_fit_lds_bytes(L) > 64 * 1024)
+        return fail(CMTTS_E_INVALID, "cmtts_internal_duration_fit: bad argument");
+    k_duration_fit(d_rounded, cum, mel_len, src_lens, seg, target, unmet, B, L, n_seg, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // ---- options.  Three tiers:
 //   cmtts_set_option            process-wide SCHEDULING knobs of the public ABI: they never change a result bit
 //   cmtts_model_set_option /    per-handle NUMERICS choices (another fp32 summation order / another operand precision):
@@ -2552,6 +2574,27 @@ int cmtts_set_control_tables(cmtts_model* m, const cmtts_control_tables* t) {
     if ((t->d || t->e || t->p) && t->ld <= 0)
         return fail(CMTTS_E_INVALID, "cmtts_set_control_tables: ld (the row pitch = L of the next text-side call) must be > 0");
     m->ct = *t;
+    return 0;
+}
+
+int cmtts_set_duration_targets(cmtts_model* m, const cmtts_duration_targets* t) {
+    if (!m) return fail(CMTTS_E_INVALID, "cmtts_set_duration_targets: null model");
+    const cmtts_duration_targets off = {nullptr, nullptr, nullptr, 0, 0};
+    if (!t) { m->dt = off; return 0; }
+    if (!t->target) return fail(CMTTS_E_INVALID, "cmtts_set_duration_targets: target is required (NULL struct clears)");
+    if (t->ld <= 0) return fail(CMTTS_E_INVALID, "cmtts_set_duration_targets: ld (the row pitch = L of the next text-side call) must be > 0");
+    if (t->n_seg < 1 || (!t->seg && t->n_seg != 1))
+        return fail(CMTTS_E_INVALID, "cmtts_set_duration_targets: n_seg must be >= 1, and 1 without a segment table");
+    m->dt = *t;
+    return 0;
+}
+
+int cmtts_phoneme_marks(const float* d_rounded, const int64_t* src_lens, int B, int L, int T, int hop, int up, int down,
+                        int32_t* marks, void* stream) {
+    if (!d_rounded || !src_lens || !marks || B <= 0 || L <= 0 || T < 0 || hop <= 0 || up <= 0 || down <= 0)
+        return fail(CMTTS_E_INVALID, "cmtts_phoneme_marks: bad argument");
+    k_phoneme_marks(d_rounded, src_lens, marks, B, L, T, hop, up, down, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

@@ -45,6 +45,11 @@ int cmtts_internal_noise_bits(const int64_t* seeds, int B, int T, int M, int fir
 // fragment16_iter, ignored elsewhere.  *need = the size of the packed stream in bytes, padding included; out == NULL only queries it.  An unknown
 // layout, a (taps, K, M) the packer does not cover or out_bytes < *need returns CMTTS_E_INVALID.
 int cmtts_internal_pack_weights(const char* layout, const float* kmajor, int taps, int K, int M, int mode, void* out, size_t out_bytes, size_t* need);
+// Measurement hook (tools/duration_fit_bench.py): duration_fit_kernel alone on the caller's buffers, the launch cmtts_text_forward adds behind its
+// durations kernel while targets are installed (cmtts_set_duration_targets: d_rounded fp32 [B][L] in place, cum int32 [B][L], mel_len int64 [B],
+// seg int32 [B][L] or NULL, target int32 [B][n_seg], unmet int32 [B] or NULL).  L up to 4096.
+int cmtts_internal_duration_fit(float* d_rounded, int* cum, int64_t* mel_len, const int64_t* src_lens, const int32_t* seg, const int32_t* target,
+                                int32_t* unmet, int B, int L, int n_seg, void* stream);
 #ifdef __cplusplus
 }
 #endif

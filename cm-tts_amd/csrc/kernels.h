@@ -55,6 +55,14 @@ void k_ln_linear_energy(const float* x, const float* gamma, const float* beta, f
 bool k_ln_linear(const float* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias, float* out,
                  const int64_t* ln_lens, const int64_t* out_lens, int B, int T, int ld, int O, hipStream_t s);
 void k_cumsum_durations(const float* dur, int* cum, int64_t* mel_len, int B, int L, hipStream_t s);
+// duration targets (duration_fit.hip): behind a durations kernel, the integer durations of each segment apportioned to its target frame count
+// (largest remainder, exact integers; seg NULL = one segment per utterance); rewrites d_rounded (integers as fp32), cum, mel_len; unmet [B] or NULL
+size_t k_duration_fit_lds_bytes(int L);      // the workgroup's dynamic LDS
+void k_duration_fit(float* d_rounded, int* cum, int64_t* mel_len, const int64_t* src_lens, const int32_t* seg, const int32_t* target,
+                    int32_t* unmet, int B, int L, int n_seg, hipStream_t s);
+// marks int32 [B][L][4] = start frame, end frame, start sample, end sample of every phoneme (frames clipped to T when T > 0)
+void k_phoneme_marks(const float* d_rounded, const int64_t* src_lens, int32_t* marks, int B, int L, int T, int hop, int up, int down,
+                     hipStream_t s);
 void k_mel2ph(const int* cum, int64_t* mel2ph, int B, int L, int T, hipStream_t s);
 void k_length_regulate(const float* out1, const int64_t* mel2ph, float* xlr, int B, int C, int ldl,
                        int T, hipStream_t s, const float* padv = nullptr);     // padv [C]: value of padding frames (default 0)

@@ -108,6 +108,7 @@ struct cmtts_model {
     int ffn2_split = 1;    // FFT blocks: the FFN linear as 8 partial GEMMs over K segments + one reduction (another fp32 summation order than one launch: a property of the model handle, cmtts_model_set_option)
     cmtts_variance_controls vc = {1.f, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     cmtts_control_tables ct = {nullptr, nullptr, nullptr, 0};      // per-phoneme control tables [B][ld] (cmtts_set_control_tables); a table replaces the scalar of its control
+    cmtts_duration_targets dt = {nullptr, nullptr, nullptr, 0, 0};      // duration targets [B][n_seg] (cmtts_set_duration_targets): the fit runs behind the durations kernel
     Allocs al;
     float *embed = nullptr, *omega_h = nullptr, *omega_cwt = nullptr, *omega_res = nullptr;
     float *pe_h = nullptr, *pe_cwt = nullptr;   // sinusoid tables [PE_ROWS][C]

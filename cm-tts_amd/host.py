@@ -104,6 +104,84 @@ class _InstalledTables:
             self.active = False
 
 
+def _resolve_targets(B, L, target_frames=None, segments=None, d_targets=None):
+    """The duration targets of a call over B utterances padded to L phonemes (cmtts_set_duration_targets; the definition:
+    timing.fit_segments).  target_frames: an integer tensor [B] (frames per utterance), or [B, G] with segments, an integer tensor
+    [B, L] that names each phoneme's segment in [-1, G) (-1: in none); a target of -1 leaves its utterance / segment alone.
+    Returns None, or (target int32 [B, G] CPU, seg int32 [B, L] CPU or None), validated here, before anything launches — ValueError
+    for a wrong type, dtype, shape or range, segments without targets, or targets beside d_targets (absolute durations leave
+    nothing to fit)."""
+    from .timing import MAX_TARGET
+    if target_frames is None:
+        if segments is not None:
+            raise ValueError("segments: needs target_frames [B, G]")
+        return None
+    if d_targets is not None:
+        raise ValueError("target_frames: not beside d_targets (absolute durations leave nothing to fit)")
+    out = []
+    for name, v in (("target_frames", target_frames), ("segments", segments)):
+        if v is None:
+            out.append(None)
+            continue
+        if isinstance(v, np.ndarray):
+            v = torch.from_numpy(v)
+        if not isinstance(v, torch.Tensor):
+            raise ValueError(f"{name}: an integer tensor, not {type(v).__name__}")
+        if v.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{name}: the tensor must be int32 or int64, not {v.dtype}")
+        out.append(v.detach().to("cpu"))
+    tgt, seg = out
+    if seg is None:
+        if tuple(tgt.shape) != (B,):
+            raise ValueError(f"target_frames: shape {tuple(tgt.shape)}, expected [{B}] (with segments: [{B}, G])")
+        tgt = tgt[:, None]
+    else:
+        if tgt.dim() != 2 or tgt.shape[0] != B or tgt.shape[1] < 1:
+            raise ValueError(f"target_frames: shape {tuple(tgt.shape)}, expected [{B}, G] beside segments")
+        if tuple(seg.shape) != (B, L):
+            raise ValueError(f"segments: shape {tuple(seg.shape)}, expected [{B}, {L}]")
+        G = int(tgt.shape[1])
+        if seg.numel() and (int(seg.min()) < -1 or int(seg.max()) >= G):
+            raise ValueError(f"segments: every entry must lie in [-1, {G})")
+        seg = seg.to(torch.int32).contiguous()
+    if tgt.numel() and (int(tgt.min()) < -1 or int(tgt.max()) > MAX_TARGET):
+        raise ValueError(f"target_frames: every target must lie in [0, {MAX_TARGET}], or be -1 (leave alone)")
+    return tgt.to(torch.int32).contiguous(), seg
+
+
+class _InstalledTargets:
+    """The duration targets of one call on the device, installed on the model (cmtts_set_duration_targets); clear() in a finally.
+    lo / hi: the rows of a rank's slice (text_state_records).  clear() does not synchronise: the launch has captured the pointers,
+    the tensors were allocated on the calling stream and the caching allocator hands their memory out again in that stream's order."""
+
+    def __init__(self, model, targets, L, lo=None, hi=None):
+        self.model, self.unmet, self.active = model, None, targets is not None
+        if not self.active:
+            return
+        tgt, seg = targets
+        if lo is not None:
+            tgt, seg = tgt[lo:hi], (None if seg is None else seg[lo:hi])
+        dev = model.device
+        self.tgt = tgt.to(dev).contiguous()
+        self.seg = None if seg is None else seg.to(dev).contiguous()
+        self.unmet = torch.zeros(int(tgt.shape[0]), dtype=torch.int32, device=dev)
+        dt = _lib.DurationTargetsStruct(seg=_ptr(self.seg), target=_ptr(self.tgt), unmet=_ptr(self.unmet), ld=int(L), n_seg=int(tgt.shape[1]))
+        _lib.check(model.lib.cmtts_set_duration_targets(model._h, C.byref(dt)))
+
+    def clear(self):
+        if self.active:
+            self.model.lib.cmtts_set_duration_targets(self.model._h, None)
+            self.active = False
+
+    def raise_unmet(self, first=0):
+        """After a read-back has synchronised the stream: ValueError naming the utterances with a segment that could not be met."""
+        if self.unmet is not None:
+            bad = [(first + b, int(k)) for b, k in enumerate(self.unmet.cpu().tolist()) if k > 0]
+            if bad:
+                raise ValueError("target_frames: " + ", ".join(f"utterance {b}: {k} segment(s)" for b, k in bad) +
+                                 " with a target > 0 hold only phonemes of 0 frames and cannot be met")
+
+
 def _push_state_dict(lib, setter, handle, sd):
     for name, v in sd.items():
         if isinstance(v, torch.Tensor):
@@ -309,12 +387,17 @@ class DurationPitchSpeakerNet(torch.nn.Module):
 
     def forward(self, speakers=None, texts=None, src_lens=None, mels=None, mel_lens=None, p_targets=None,
                 e_targets=None, d_targets=None, mel2phs=None, spker_embeds=None,
-                p_control=1.0, e_control=1.0, d_control=1.0, max_mel_len=None, **kwargs):
+                p_control=1.0, e_control=1.0, d_control=1.0, max_mel_len=None, target_frames=None, segments=None, **kwargs):
         """p_targets = {"cwt_spec" [B,T,10], "f0_mean" [B], "f0_std" [B], "uv" bool [B,T]}, e_targets [B,L],
         d_targets [B,L] as in the reference.  `mel2phs` is accepted and ignored: mel2ph is recomputed from
         d_targets (dur_to_mel2ph), which is what the reference's dataset stores.
         p_control / e_control / d_control: a number, or a float32 tensor [B] (one factor per utterance) or [B, L] (one per phoneme):
-        the tables of cmtts_set_control_tables (model/modules.py:270, 326, 369 are elementwise)."""
+        the tables of cmtts_set_control_tables (model/modules.py:270, 326, 369 are elementwise).
+        target_frames / segments: duration targets (_resolve_targets; cmtts_set_duration_targets) — each utterance, or each segment of
+        it, takes exactly its target's frames (timing.fit_segments on the controlled integer durations; timing.frames_for_seconds
+        turns seconds into frames, to within half a frame).  "d_rounded" then holds the fitted integers.  A segment that cannot be
+        met (a target > 0 over phonemes of 0 frames) raises ValueError after the mel_len read-back; when mels / max_mel_len fix T
+        there is no read-back and the counts come back as "unmet_targets" (int32 [B], device) for the caller to judge."""
         o = self._owner
         if texts is None:
             o._require()
@@ -322,6 +405,7 @@ class DurationPitchSpeakerNet(torch.nn.Module):
         if len(tshape) != 2:
             raise ValueError("texts must be [B, L]")
         (p_control, e_control, d_control), tabs = _resolve_controls(tshape[0], tshape[1], p_control, e_control, d_control)
+        targets = _resolve_targets(tshape[0], tshape[1], target_frames, segments, d_targets)
         o._require()
         cfg, lib, dev = o.config, o.lib, o.device
         vc, keep = None, []
@@ -366,9 +450,10 @@ class DurationPitchSpeakerNet(torch.nn.Module):
             tws = o._ws.get("text", nb, dev)
             if vc is not None:
                 _lib.check(lib.cmtts_set_variance_controls(o._h, C.byref(vc)))
-            inst = None
+            inst = fit = None
             try:
                 inst = _InstalledTables(o, tabs, L)
+                fit = _InstalledTargets(o, targets, L)
                 _lib.check(lib.cmtts_text_forward(o._h, _ptr(texts), _ptr(src_lens), _ptr(spk_in), _ptr(spk_ids), B, L, float(d_control),
                                                   _ptr(log_d), _ptr(d_rounded), _ptr(mel_len), _ptr(e_pred), _ptr(e_idx),
                                                   _ptr(enc_ct), _ptr(spk), _ptr(tws), nb, _stream()))
@@ -378,6 +463,7 @@ class DurationPitchSpeakerNet(torch.nn.Module):
                     T = int(max_mel_len)
                 else:
                     T = int(mel_len.max().item())               # the one host read-back (pad() batch max)
+                    fit.raise_unmet()
                 O = cfg.cwt_out
                 cond_ct = f(B, H, T)
                 mel2ph = torch.empty(B, T, dtype=torch.int64, device=dev)
@@ -394,6 +480,8 @@ class DurationPitchSpeakerNet(torch.nn.Module):
                 _lib.check(lib.cmtts_frame_forward_sub_t(o._h, _ptr(tws), B, L, 0, B, T, _ptr(cond_ct), _ptr(mel2ph), _ptr(cwt),
                                                          _ptr(f0), _ptr(p_idx), _ptr(stats), _ptr(p1), _ptr(p1t), _ptr(fws), nf, _stream()))
             finally:
+                if fit is not None:
+                    fit.clear()
                 if inst is not None:
                     inst.clear()
                 if vc is not None:
@@ -402,7 +490,9 @@ class DurationPitchSpeakerNet(torch.nn.Module):
         mel_masks = get_mask_from_lengths(mel_len, T)
         factors = None if p1 is None else CondFactors(p1, p1_ld, L, mel2ph, p_idx, cond_ct, p1t)
         cond_ct._cmtts_factors = factors       # rides along with THIS tensor object: sample_with_cond(cond_ct, ...) finds it (and re-checks it)
+        extra = {} if fit.unmet is None else {"unmet_targets": fit.unmet}
         return {
+            **extra,
             "cond": cond_ct.transpose(1, 2),               # [B,T,H] view of the channel-major buffer
             "cond_ct": cond_ct,
             "cond_factors": factors,
@@ -1276,19 +1366,48 @@ def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_
                 p[3].synchronize()
 
 
+def phoneme_marks(out, T=None, sample_rate=None, vocoder=None):
+    """Where each phoneme lies in the delivered audio: int32 [B, L, 4] on the device = start frame, end frame, start sample, end
+    sample (cmtts_phoneme_marks; the definition: timing.phoneme_marks).  out: what DurationPitchSpeakerNet.forward returned (its
+    "d_rounded" and "src_lens").  T: clip the frames to a mel cut at T frames (default: none).  sample_rate: the output rate the
+    audio is delivered at (vocoder_infer / vocoder_infer_stream's); None = the native rate, up = down = 1.  vocoder: supplies the hop
+    (default: the V1 generator's 256)."""
+    from . import resample as _resample
+    d, src = out["d_rounded"], out["src_lens"]
+    hop = vocoder.h.hop if vocoder is not None else _resample.HOP
+    up, down = (1, 1) if sample_rate is None else _resample.ratio(_resample.NATIVE_RATE, sample_rate)      # as _output_format
+    T = 0 if T is None else int(T)
+    if T < 0:
+        raise ValueError(f"phoneme_marks: T = {T}")
+    B, L = d.shape
+    lib = _lib.load()
+    with torch.cuda.device(d.device):
+        marks = torch.empty(B, L, 4, dtype=torch.int32, device=d.device)
+        _lib.check(lib.cmtts_phoneme_marks(_ptr(d), _ptr(src), B, L, T, int(hop), int(up), int(down), _ptr(marks), _stream()))
+    return marks
+
+
 def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=None, speakers=None, n_steps=4, noise=None,
                       chunk_frames=STREAM_CHUNK_FRAMES, generator=None, max_wav_value=32768.0,
-                      p_control=1.0, e_control=1.0, d_control=1.0, seeds=None, sample_rate=None, encoding="s16"):
+                      p_control=1.0, e_control=1.0, d_control=1.0, seeds=None, sample_rate=None, encoding="s16",
+                      target_frames=None, segments=None, on_marks=None):
     """Text -> streamed PCM: the duration net and the T-step sampler exactly as CMTotalTTSSynthesize.synthesize runs them (noise
     [n_noise, B, 1, T, 80] drawn as x0 = randn, then randn_like(x0) per further step, unless given), then vocoder_infer_stream on
     the mels trimmed to their predicted lengths.  Yields (utterance, sample_offset, pcm int16 numpy, is_last).
     p_control / e_control / d_control: numbers, [B] or [B, L] float32 tensors (DurationPitchSpeakerNet.forward).
     seeds: int64 [B] utterance seeds or one int — seeded noise generated by the sampler (sample_with_cond), in place of noise / generator.
-    sample_rate / encoding: the output format (vocoder_infer_stream); offsets then count output samples."""
+    sample_rate / encoding: the output format (vocoder_infer_stream); offsets then count output samples.
+    target_frames / segments: duration targets (DurationPitchSpeakerNet.forward): utterance b's chunks then concatenate to exactly
+    out_len(target * hop) samples.
+    on_marks: a callable that receives phoneme_marks(...) as int32 numpy [B, L, 4] once, before the first chunk is handed out, in the
+    stream's own output rate — the scale of the chunk offsets.  What the generator yields does not change."""
     if seeds is not None and noise is not None:
         raise ValueError("synthesize_stream: give noise or seeds, not both")
+    if on_marks is not None and not callable(on_marks):
+        raise ValueError("synthesize_stream: on_marks must be callable")
     out = model.duration_pitch_energy_net(speakers=speakers, texts=texts, src_lens=src_lens, spker_embeds=spker_embeds,
-                                          p_control=p_control, e_control=e_control, d_control=d_control)
+                                          p_control=p_control, e_control=e_control, d_control=d_control,
+                                          target_frames=target_frames, segments=segments)
     B, T, _ = out["cond"].shape
     cfg = model.config
     if n_steps not in (1, 2, 4):
@@ -1298,6 +1417,8 @@ def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=
         noise = _draw_sampler_noise(generator or DummyGenerator(), B, T, cfg.n_mels, draws, model.device)
     mel = sample_with_cond(model, out["cond_ct"], out["speaker_emb"], n_steps, noise, factors=out.get("cond_factors"), seeds=seeds)
     mel_lens = out["mel_lens"].cpu().tolist()
+    if on_marks is not None:
+        on_marks(phoneme_marks(out, sample_rate=sample_rate, vocoder=vocoder).cpu().numpy())
     yield from vocoder_infer_stream(mel.transpose(1, 2), vocoder, mel_lens, chunk_frames, max_wav_value, sample_rate=sample_rate,
                                     encoding=encoding)
 
@@ -1727,13 +1848,16 @@ class CMTotalTTSSynthesize:
         model.eval()
         return model, diffusion
 
-    def synthesize(self, batch, p_control=None, e_control=None, d_control=None, seeds=None):
+    def synthesize(self, batch, p_control=None, e_control=None, d_control=None, seeds=None, target_frames=None, segments=None):
         """batch = (ids, raw_texts, speakers, texts, src_lens, max_src_len, spker_embeds) after to_device (:88-153).
         The controls given at construction apply (numbers, or float32 [B] / [B, L] tensors); a control given here replaces the
         constructor's for this call — a table on top of a constructor scalar other than 1 is a ValueError.
         seeds: int64 [B] utterance seeds or one int — the sampler generates the seeded noise itself (sample_with_cond) and the
-        generator is not drawn from.  A "determ-indiv" generator (get_generator) without `seeds` does the same with its own seeds."""
+        generator is not drawn from.  A "determ-indiv" generator (get_generator) without `seeds` does the same with its own seeds.
+        target_frames / segments: duration targets (DurationPitchSpeakerNet.forward) — out_put[11] are then the fitted lengths."""
         kw = {"speakers": batch[2], "texts": batch[3], "src_lens": batch[4], "spker_embeds": batch[-1]}
+        if target_frames is not None or segments is not None:
+            kw["target_frames"], kw["segments"] = target_frames, segments
         _check_no_scalar_with_table((self.p_control, self.e_control, self.d_control), p_control, e_control, d_control)
         for name, own, given in (("p_control", self.p_control, p_control), ("e_control", self.e_control, e_control),
                                  ("d_control", self.d_control, d_control)):
@@ -1742,6 +1866,7 @@ class CMTotalTTSSynthesize:
                 kw[name] = v
         tshape = tuple(torch.as_tensor(kw["texts"]).shape)
         _resolve_controls(tshape[0], tshape[-1], kw.get("p_control", 1.0), kw.get("e_control", 1.0), kw.get("d_control", 1.0))
+        _resolve_targets(tshape[0], tshape[-1], target_frames, segments)
         out_dict = self.duration_pitch_energy_net(**kw)
         B, T, _ = out_dict["cond"].shape
         cfg = self.model.config
@@ -1759,6 +1884,8 @@ class CMTotalTTSSynthesize:
         gen = self.generator or DummyGenerator()
         if seeds is not None and not fusable:
             raise NotImplementedError("seeds: the fused sampler only (a distilled model with the config's sigmas)")
+        if target_frames is not None and not fusable:      # the host-side loops re-run the duration net from the reference's argument list
+            raise NotImplementedError("target_frames: the fused sampler only (a distilled model with the config's sigmas)")
         if not fusable:      # e.g. a progdist teacher: the reference's sampler loops, host-side (karras_sample_tts routes)
             sample = karras_sample_tts(self.diffusion, self.model, (B, 1, T, cfg.n_mels), steps=2, model_kwargs=kw,
                                        device=self.device, sigma_min=float(cm.get("sigma_min", cfg.sigma_min)),
@@ -1824,16 +1951,20 @@ def utterance_noise(seed, index, n_noise, T, n_mels, device):
 
 
 def text_state_records(model: CMTotalTTS, texts, src_lens, lo, hi, spker_embeds=None, speakers=None, d_control=1.0,
-                       e_control=1.0, p_control=1.0):
+                       e_control=1.0, p_control=1.0, target_frames=None, segments=None):
     """Text side of utterances [lo, hi) of a batch padded to L_all = texts.shape[1] phonemes (the reference's batch padding,
     cmtts_text_forward), packed into text-state records.  Returns (records uint8 [hi - lo, R], mel_len int64 [hi - lo]) on the
     model's device.  d_control / e_control / p_control: numbers, or float32 tensors [B] / [B, L_all] over the WHOLE batch (global
     utterance index): rows [lo, hi) are the tables of this call; with a p_control table the records carry its rows (layout
     revision 2) for the frame side.  A scalar e_control / p_control other than 1 is set with cmtts_set_variance_controls by the
-    caller around both phases (synthesize_sharded), not here."""
+    caller around both phases (synthesize_sharded), not here.
+    target_frames / segments: duration targets over the WHOLE batch ([B] / [B, G] and [B, L_all], global utterance index), rows
+    [lo, hi) taken here; the records carry the fitted cum, so the frame side needs nothing more.  A segment that cannot be met
+    raises ValueError (one read-back of hi - lo counters)."""
     o = model
     L = int(texts.shape[1])
     (p_s, e_s, d_control), tabs = _resolve_controls(int(texts.shape[0]), L, p_control, e_control, d_control)
+    targets = _resolve_targets(int(texts.shape[0]), L, target_frames, segments)
     if p_s != 1.0 or e_s != 1.0:
         raise ValueError("text_state_records: scalar p_control / e_control are variance controls of both phases "
                          "(cmtts_set_variance_controls around them, as synthesize_sharded does); pass tables or 1.0 here")
@@ -1863,9 +1994,10 @@ def text_state_records(model: CMTotalTTS, texts, src_lens, lo, hi, spker_embeds=
         mel_len = torch.empty(n, dtype=torch.int64, device=dev)
         nb = lib.cmtts_text_workspace_bytes(o._h, n, L)
         tws = o._ws.get("text_sharded", nb, dev)
-        inst = None
+        inst = fit = None
         try:
             inst = _InstalledTables(o, tabs, L, lo, hi)      # this rank's utterances, selected by global index
+            fit = _InstalledTargets(o, targets, L, lo, hi)
             R = lib.cmtts_text_state_record_bytes(o._h, L)
             _lib.check(lib.cmtts_text_forward(o._h, _ptr(tx), _ptr(sl), _ptr(spk_in), _ptr(ids), n, L, float(d_control),
                                               None, None, _ptr(mel_len), None, None, None, None, _ptr(tws), nb, _stream()))
@@ -1873,7 +2005,10 @@ def text_state_records(model: CMTotalTTS, texts, src_lens, lo, hi, spker_embeds=
             gidx = torch.arange(lo, hi, dtype=torch.int64, device=dev)
             records = torch.empty(n, R, dtype=torch.uint8, device=dev)
             _lib.check(lib.cmtts_text_state_pack(o._h, _ptr(tws), n, L, _ptr(rows), n, _ptr(gidx), _ptr(sl), _ptr(records), _stream()))
+            fit.raise_unmet(lo)
         finally:
+            if fit is not None:
+                fit.clear()
             if inst is not None:
                 inst.clear()
     return records, mel_len
@@ -1948,7 +2083,7 @@ def _frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, d
 
 def synthesize_sharded(model: CMTotalTTS, texts, src_lens, spker_embeds=None, speakers=None, n_steps=4, group=None, seed=0,
                        buckets=None, vocoder=None, d_control=1.0, p_control=1.0, e_control=1.0, tail_frames=16, max_wav_value=32768.0,
-                       seeds=None):
+                       seeds=None, target_frames=None, segments=None):
     """A batch of texts (synthesize.py batch mode: texts int64 [B, L], src_lens [B], the same on every rank) over the ranks of
     `group` (torch.distributed; none initialised = one rank): text side of this rank's slice (shard.shard_range), lengths agreed,
     text-state records moved to the ranks of the agreed plan_shards(mel_len) (shard.two_phase), frame side and sampler per bucket,
@@ -1960,7 +2095,9 @@ def synthesize_sharded(model: CMTotalTTS, texts, src_lens, spker_embeds=None, sp
     "plan": the plan; with `vocoder`: "wavs": [int16 [len_i * 256]] (shard.allgather_pcm per bucket)}.
     d_control / p_control / e_control: numbers, or float32 tensors [B] (per utterance) / [B, L] (per phoneme, L = texts.shape[1])
     indexed by GLOBAL utterance: every rank passes the same tables, each takes the rows of its own utterances for the text
-    side, and the pitch rows travel inside the text-state records to the rank that runs the utterance's frame side."""
+    side, and the pitch rows travel inside the text-state records to the rank that runs the utterance's frame side.
+    target_frames / segments: duration targets by GLOBAL utterance ([B] / [B, G] and [B, L]; DurationPitchSpeakerNet.forward): each
+    rank fits the rows of its own slice, and the fitted lengths are what the ranks agree the plan on."""
     from . import shard
     if buckets is None:
         buckets = shard.FRAME_BUCKETS
@@ -1972,6 +2109,9 @@ def synthesize_sharded(model: CMTotalTTS, texts, src_lens, spker_embeds=None, sp
         seeds = _device_seeds(seeds, n_items, "cpu").numpy()
     (p_control, e_control, d_control), tabs = _resolve_controls(n_items, int(texts.shape[1]), p_control, e_control, d_control)
     tabs = {k: t[:, :L_all].contiguous() for k, t in tabs.items()}      # the tables are as wide as `texts` and cut with it
+    targets = _resolve_targets(n_items, int(texts.shape[1]), target_frames, segments)
+    tf_arg = None if targets is None else (targets[0] if targets[1] is not None else targets[0][:, 0])
+    seg_arg = None if targets is None or targets[1] is None else targets[1][:, :L_all].contiguous()
     texts = texts[:, :L_all]
     d_arg, e_arg, p_arg = tabs.get("d", d_control), tabs.get("e", 1.0), tabs.get("p", 1.0)
     model._require()
@@ -1983,7 +2123,8 @@ def synthesize_sharded(model: CMTotalTTS, texts, src_lens, spker_embeds=None, sp
     try:
         res = shard.two_phase(
             n_items,
-            lambda lo, hi: text_state_records(model, texts, src_lens, lo, hi, spker_embeds, speakers, d_arg, e_arg, p_arg),
+            lambda lo, hi: text_state_records(model, texts, src_lens, lo, hi, spker_embeds, speakers, d_arg, e_arg, p_arg,
+                                              target_frames=tf_arg, segments=seg_arg),
             lambda groups: frame_side_from_records(model, groups, L_all, n_steps, seed, tail_frames, p_control=p_arg, seeds=seeds),
             group=group, buckets=buckets)
         if vocoder is not None:

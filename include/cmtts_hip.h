@@ -66,7 +66,8 @@ const char* cmtts_version(void);
  * 8 — options only: cmtts_model_set_option / cmtts_vocoder_set_option "batch_invariant" (a host detects support here);
  * still 8 — cmtts_set_control_tables (per-phoneme control tables) is a new entry point and a new struct: no existing layout or
  * signature changes, so the number stays; a host detects it by looking the symbol up (dlsym).  Likewise the resampler
- * (cmtts_resampler_*, cmtts_resample_encode) and cmtts_vocoder_forward_windows_f32: entry points only, still 8.
+ * (cmtts_resampler_*, cmtts_resample_encode) and cmtts_vocoder_forward_windows_f32: entry points only, still 8; and the duration
+ * targets (cmtts_set_duration_targets, a new struct) with cmtts_phoneme_marks: entry points only, still 8.
  * A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
  * against before it passes a struct (cmtts_amd/_lib.py does at load time). */
 #define CMTTS_ABI_VERSION 8
@@ -156,6 +157,46 @@ typedef struct cmtts_control_tables {
     int ld;
 } cmtts_control_tables;
 int cmtts_set_control_tables(cmtts_model* m, const cmtts_control_tables* t);
+
+/* ---- Duration targets: an utterance, or segments of it (words, a subtitle cue), fitted to an exact number of frames.  The reference has
+ * only the multiplier (model/modules.py:369-372), and sum(int(round(exp(log_d) - 1) * d)) is a step function of d that in general hits
+ * no given length; the definition is this library's (cmtts_amd/timing.py is its executable form).  With targets
+ * installed cmtts_text_forward(_ragged) runs one more kernel behind its durations kernel (the scalar or the table form, so relative
+ * emphasis from d_control or a duration table survives).  Per utterance b and segment g with t = target[b, g] >= 0, over the phonemes
+ * l < src_lens[b] with seg[b, l] = g in index order, n = max((int)d_rounded, 0) and S = sum n:
+ *     q = n t,  a = q / S,  r = q % S,  R = t - sum a      (exact 64-bit integers)
+ *     the R phonemes with the largest r get a + 1 frames, the others a; equal r: the lower index first.
+ * So the segment has exactly t frames, a phoneme of 0 frames keeps 0, every phoneme is within one frame of n t / S, and t = S changes
+ * nothing.  S = 0 leaves the segment as it is; with t > 0 it could not be met and is counted in unmet[b].  d_rounded then holds the
+ * INTEGER frame counts (as fp32, every phoneme of the batch, also outside all segments), cum and mel_len their sums; log_d is not
+ * touched.  Everything downstream — mel2ph, the length regulator, the pitch table, the text-state records — reads cum and mel_len
+ * only, so a fitted length travels through the frame side, the sampler, streaming and a sharded synthesis unchanged.
+ *   seg    int32 [B, ld] DEVICE: the segment of each phoneme, -1 = in none (left alone); NULL = one segment per utterance holding all
+ *          its phonemes (n_seg must then be 1)
+ *   target int32 [B, n_seg] DEVICE: frames per segment, -1 = leave alone
+ *   unmet  int32 [B] DEVICE or NULL: written by every text-side call while installed
+ *   ld     = the L of the next text-side call; another L is CMTTS_E_INVALID there (and L above 4096, the kernel's LDS)
+ * Targets together with a teacher-forced d_target (cmtts_set_variance_controls) are CMTTS_E_INVALID at the forward call: absolute
+ * durations leave nothing to fit.  The caller's contract, as for all device data: 0 <= target <= 1 << 24 (a frame count is returned
+ * as fp32) or -1; seg in [-1, n_seg); entries at l >= src_lens[b] are ignored.  (A seg value outside the range is treated as -1.)
+ * A frame is the model's unit: a length asked for in seconds is met to within half a frame, hop / (2 sampling_rate) s.
+ * Without targets the text side's launch sequence is unchanged.  The targets stay on the model until replaced; NULL clears them;
+ * the pointers must stay valid while the forward calls run. */
+typedef struct cmtts_duration_targets {
+    const int32_t* seg;
+    const int32_t* target;
+    int32_t* unmet;
+    int ld, n_seg;
+} cmtts_duration_targets;
+int cmtts_set_duration_targets(cmtts_model* m, const cmtts_duration_targets* t);
+/* Where each phoneme lies in the delivered audio: marks int32 [B, L, 4] DEVICE = start frame, end frame, start sample, end sample.
+ * Frames are the cumulative sums of max((int)d_rounded[b, l], 0) over l < src_lens[b] (d_rounded fp32 [B, L] as cmtts_text_forward
+ * returned it, src_lens int64 [B]: no text workspace is read), clipped to T when T > 0 (a mel cut at T frames; T = 0: no clipping);
+ * samples are ceil(frame * hop * up / down): up / down = output rate / native rate in lowest terms (1, 1 = native), the mapping of
+ * the streamed vocoder's chunk offsets (cmtts_resample_encode), so a mark and a chunk offset are on one scale.  Rows l >= src_lens[b]
+ * repeat the utterance's end. */
+int cmtts_phoneme_marks(const float* d_rounded, const int64_t* src_lens, int B, int L, int T, int hop, int up, int down,
+                        int32_t* marks, void* stream);
 
 /* ---- frame-level half (model/modules.py:373-412; LengthRegulator :415-448; dur_to_mel2ph
  * utils/tools.py:768-798; get_pitch_embedding cwt branch :259-317).  T = padded frame count chosen
