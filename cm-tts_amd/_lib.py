@@ -103,6 +103,10 @@ SIGNATURES = {
     "cmtts_resampler_half_width": (_i, [_vp]),
     "cmtts_resample_encode": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _f, _vp, _i64, _vp]),
     "cmtts_vocoder_forward_windows_f32": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "cmtts_loudness_coefficients": (_i, [_i, C.POINTER(C.c_double)]),
+    "cmtts_loudness_workspace_bytes": (_i64, [_i, _i64, _i]),
+    "cmtts_loudness_measure": (_i, [_vp, _i, _i64, _vp, _i, _vp, _f, _vp, _vp, _sz, _vp]),
+    "cmtts_resample_encode_gain": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _f, _vp, _i64, _vp, _vp]),
     "cmtts_profile_begin": (_i, [_i, _i]),
     "cmtts_set_fused_resblock": (_i, [_i]),
     "cmtts_set_persistent_denoiser": (_i, [_i]),

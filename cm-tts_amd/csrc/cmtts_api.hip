@@ -27,6 +27,7 @@
 #include "text_state.h"
 #include "stream_windows.h"
 #include "resample.h"
+#include "loudness.h"
 #include "noise_philox.h"
 
 
@@ -2334,9 +2335,8 @@ int cmtts_resampler_half_width(const cmtts_resampler* r) {
     if (!r) return fail(CMTTS_E_INVALID, "cmtts_resampler_half_width: null argument");
     return r->R;
 }
-int cmtts_resample_encode(cmtts_resampler* r, const float* wav, int rows, int64_t ld, const int32_t* segments, int N, int encoding,
-                          float max_wav_value, void* out, int64_t out_ld, void* stream) {
-    const char* who = "cmtts_resample_encode";
+static int resample_encode(const char* who, cmtts_resampler* r, const float* wav, int rows, int64_t ld, const int32_t* segments, int N,
+                           int encoding, float max_wav_value, void* out, int64_t out_ld, const float* gains, void* stream) {
     if (!r || !wav || !segments || !out) return fail(CMTTS_E_INVALID, std::string(who) + ": null argument");
     if (rows <= 0 || ld <= 0 || N <= 0 || N > 65535 || out_ld <= 0)
         return fail(CMTTS_E_INVALID, std::string(who) + ": rows, ld, N and out_ld must be positive (N <= 65535)");
@@ -2375,8 +2375,55 @@ int cmtts_resample_encode(cmtts_resampler* r, const float* wav, int rows, int64_
         r->seg_cap = cap;
     }
     HIPCHK(hipMemcpyAsync(r->seg, segments, (size_t)N * sizeof(ResampleSegment), on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-    const int rc = cmtts_launch_resample_encode(wav, (long)ld, r->seg, N, r->table, r->L, r->M, r->R, encoding, max_wav_value, out, (long)out_ld, (void*)s);
+    const int rc = cmtts_launch_resample_encode_gain(wav, (long)ld, r->seg, N, r->table, r->L, r->M, r->R, encoding, max_wav_value, out,
+                                                     (long)out_ld, gains, (void*)s);
     if (rc != 0) return fail(CMTTS_E_HIP, "resample_encode launch failed");
+    return 0;
+}
+int cmtts_resample_encode(cmtts_resampler* r, const float* wav, int rows, int64_t ld, const int32_t* segments, int N, int encoding,
+                          float max_wav_value, void* out, int64_t out_ld, void* stream) {
+    return resample_encode("cmtts_resample_encode", r, wav, rows, ld, segments, N, encoding, max_wav_value, out, out_ld, nullptr, stream);
+}
+int cmtts_resample_encode_gain(cmtts_resampler* r, const float* wav, int rows, int64_t ld, const int32_t* segments, int N, int encoding,
+                               float max_wav_value, void* out, int64_t out_ld, const float* gains, void* stream) {
+    return resample_encode("cmtts_resample_encode_gain", r, wav, rows, ld, segments, N, encoding, max_wav_value, out, out_ld, gains, stream);
+}
+
+// ---- loudness measurement and output gain (loudness.hip, loudness_coef.cpp)
+int cmtts_loudness_coefficients(int fs, double* out10) {
+    if (!out10) return fail(CMTTS_E_INVALID, "cmtts_loudness_coefficients: null argument");
+    if (loudness_coefficients(fs, out10) != 0)
+        return fail(CMTTS_E_INVALID, "cmtts_loudness_coefficients: fs must be a multiple of 10 in [8000, 48000]");
+    return 0;
+}
+static bool loudness_shape_ok(int rows, int64_t ld, int fs) {
+    return rows > 0 && rows <= 65535 && ld > 0 && fs >= LD_MIN_RATE && fs <= LD_MAX_RATE && fs % 10 == 0;
+}
+int64_t cmtts_loudness_workspace_bytes(int rows, int64_t ld, int fs) {
+    if (!loudness_shape_ok(rows, ld, fs)) return 0;
+    const int64_t chunk = fs / 10, n_chunks = (ld + chunk - 1) / chunk;
+    return 2 * rows * n_chunks * (int64_t)sizeof(float);          // the chunk sums and the chunk peaks, [rows][n_chunks] each
+}
+int cmtts_loudness_measure(const float* wav, int rows, int64_t ld, const int32_t* n_valid, int fs, const float* target_lufs, float ceiling_db,
+                           float* stats, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "cmtts_loudness_measure";
+    if (!wav || !n_valid || !stats || !ws) return fail(CMTTS_E_INVALID, std::string(who) + ": null argument");
+    if (!loudness_shape_ok(rows, ld, fs))
+        return fail(CMTTS_E_INVALID, std::string(who) + ": rows in [1, 65535], ld >= 1 and fs a multiple of 10 in [8000, 48000] are required");
+    if (ceiling_db != ceiling_db) return fail(CMTTS_E_INVALID, std::string(who) + ": ceiling_db is NaN");
+    if ((int64_t)ws_bytes < cmtts_loudness_workspace_bytes(rows, ld, fs)) return fail(CMTTS_E_INVALID, std::string(who) + ": workspace too small");
+    LoudnessPlan plan;
+    if (loudness_plan(fs, &plan) != 0) return fail(CMTTS_E_INVALID, std::string(who) + ": no plan for this sample rate");
+    const int64_t n_chunks = (ld + plan.chunk - 1) / plan.chunk;
+    if (n_chunks > INT_MAX) return fail(CMTTS_E_INVALID, std::string(who) + ": ld too large");
+    float* sums = (float*)ws;
+    float* peaks = sums + (size_t)rows * n_chunks;
+    int rc = cmtts_launch_loudness_chunks(wav, (long)ld, rows, n_valid, &plan, sums, peaks, (int)n_chunks, stream);
+    if (rc == -2) return fail(CMTTS_E_UNSUPPORTED, std::string(who) + ": the chunk span does not fit the kernel's LDS");
+    if (rc != 0) return fail(CMTTS_E_HIP, "loudness chunk launch failed");
+    rc = cmtts_launch_loudness_finish(sums, peaks, (int)n_chunks, (long)ld, rows, n_valid, plan.chunk, target_lufs,
+                                      (float)pow(10.0, (double)ceiling_db / 20.0), stats, stream);
+    if (rc != 0) return fail(CMTTS_E_HIP, "loudness finish launch failed");
     return 0;
 }
 int cmtts_internal_mel_window_gather(const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, float* out, void* stream) {

@@ -24,6 +24,10 @@ int cmtts_launch_resample_table(const float* taps, int L, int half, int R, float
 // [0, n_valid) and outside the row's coverage [origin, origin + ld).  -2: the tile's source span exceeds RS_MAX_SPAN.
 int cmtts_launch_resample_encode(const float* wav, long ld, const ResampleSegment* seg, int N, const float* table, int L, int M, int R,
                                  int enc, float max_wav, void* out, long out_ld, void* stream);
+// The same with a gain per SOURCE row (gains [rows], device): x is replaced by fl32(gains[row] * x), one multiplication per source sample
+// as it is staged.  gains == NULL is cmtts_launch_resample_encode: the instantiation without the multiplication.
+int cmtts_launch_resample_encode_gain(const float* wav, long ld, const ResampleSegment* seg, int N, const float* table, int L, int M, int R,
+                                      int enc, float max_wav, void* out, long out_ld, const float* gains, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -61,10 +61,12 @@ struct OutT<RS_ENC_ALAW> { using type = uint8_t; };
 // is 0).  In the accumulation lane i reads xs[j0(m_i) - R - base + d]: neighbouring lanes are floor-steps of M / L apart (2.76 at
 // 8 kHz: 2- and 3-bank strides, at most 2 lanes per bank; < 1 when up-sampling: same address, broadcast).  The tap rows come from
 // the global table (<= 90 KB, L2-resident; neighbouring lanes use rows M mod L apart, the odd row pitch 2 R + 1 spreads them).
-template <int ENC>
+// GAIN: the staging line stores gains[source row] * x (one fp32 multiplication per source sample); nothing else changes.
+template <int ENC, bool GAIN>
 __global__ __launch_bounds__(RS_TILE) void resample_encode_kernel(const float* __restrict__ wav, long ld, const ResampleSegment* __restrict__ seg,
                                                                   const float* __restrict__ table, int L, int M, int R, float max_wav,
-                                                                  typename OutT<ENC>::type* __restrict__ out, long out_ld) {
+                                                                  typename OutT<ENC>::type* __restrict__ out, long out_ld,
+                                                                  const float* __restrict__ gains) {
     using T = typename OutT<ENC>::type;
     extern __shared__ float xs[];
     const int n = blockIdx.y;
@@ -80,9 +82,13 @@ __global__ __launch_bounds__(RS_TILE) void resample_encode_kernel(const float* _
     const long base = (mf * M) / L - R;
     const int span = (int)((ml * M) / L + R - base) + 1;
     const float* xrow = wav + (long)sg.row * ld;
+    float g = 1.f;
+    if constexpr (GAIN) g = gains[sg.row];
     for (int i = threadIdx.x; i < span; i += RS_TILE) {
         const long a = base + i, rel = a - sg.origin;
-        xs[i] = (a >= 0 && a < sg.n_valid && rel >= 0 && rel < ld) ? xrow[rel] : 0.f;
+        const bool in = a >= 0 && a < sg.n_valid && rel >= 0 && rel < ld;
+        if constexpr (GAIN) xs[i] = in ? g * xrow[rel] : 0.f;
+        else xs[i] = in ? xrow[rel] : 0.f;
     }
     __syncthreads();
     if (k >= cnt) {
@@ -101,6 +107,29 @@ __global__ __launch_bounds__(RS_TILE) void resample_encode_kernel(const float* _
     else orow[k] = (uint8_t)lin2alaw(to_s16(acc, max_wav));
 }
 
+template <bool GAIN>
+int launch_encode(const float* wav, long ld, const ResampleSegment* seg, const float* table, int L, int M, int R, int enc, float max_wav, void* out,
+                  long out_ld, const float* gains, dim3 grid, size_t lds, hipStream_t s) {
+    const dim3 block(RS_TILE);
+    switch (enc) {
+        case RS_ENC_F32:
+            hipLaunchKernelGGL((resample_encode_kernel<RS_ENC_F32, GAIN>), grid, block, lds, s, wav, ld, seg, table, L, M, R, max_wav, (float*)out, out_ld, gains);
+            break;
+        case RS_ENC_S16:
+            hipLaunchKernelGGL((resample_encode_kernel<RS_ENC_S16, GAIN>), grid, block, lds, s, wav, ld, seg, table, L, M, R, max_wav, (int16_t*)out, out_ld, gains);
+            break;
+        case RS_ENC_MULAW:
+            hipLaunchKernelGGL((resample_encode_kernel<RS_ENC_MULAW, GAIN>), grid, block, lds, s, wav, ld, seg, table, L, M, R, max_wav, (uint8_t*)out, out_ld, gains);
+            break;
+        case RS_ENC_ALAW:
+            hipLaunchKernelGGL((resample_encode_kernel<RS_ENC_ALAW, GAIN>), grid, block, lds, s, wav, ld, seg, table, L, M, R, max_wav, (uint8_t*)out, out_ld, gains);
+            break;
+        default:
+            return -2;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 }  // namespace
 
 extern "C" int cmtts_launch_resample_table(const float* taps, int L, int half, int R, float* table, void* stream) {
@@ -108,29 +137,20 @@ extern "C" int cmtts_launch_resample_table(const float* taps, int L, int half, i
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-extern "C" int cmtts_launch_resample_encode(const float* wav, long ld, const ResampleSegment* seg, int N, const float* table, int L, int M, int R,
-                                            int enc, float max_wav, void* out, long out_ld, void* stream) {
+extern "C" int cmtts_launch_resample_encode_gain(const float* wav, long ld, const ResampleSegment* seg, int N, const float* table, int L, int M,
+                                                 int R, int enc, float max_wav, void* out, long out_ld, const float* gains, void* stream) {
     if (N <= 0 || out_ld <= 0) return 0;
     const long span = ((long)(RS_TILE - 1) * M) / L + 2L * R + 2;          // floor steps of a tile's last output + both half-widths
     if (span > RS_MAX_SPAN) return -2;
-    const dim3 grid(cdiv(out_ld, RS_TILE), N), block(RS_TILE);
+    const dim3 grid(cdiv(out_ld, RS_TILE), N);
     const size_t lds = (size_t)span * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    switch (enc) {
-        case RS_ENC_F32:
-            hipLaunchKernelGGL(resample_encode_kernel<RS_ENC_F32>, grid, block, lds, s, wav, ld, seg, table, L, M, R, max_wav, (float*)out, out_ld);
-            break;
-        case RS_ENC_S16:
-            hipLaunchKernelGGL(resample_encode_kernel<RS_ENC_S16>, grid, block, lds, s, wav, ld, seg, table, L, M, R, max_wav, (int16_t*)out, out_ld);
-            break;
-        case RS_ENC_MULAW:
-            hipLaunchKernelGGL(resample_encode_kernel<RS_ENC_MULAW>, grid, block, lds, s, wav, ld, seg, table, L, M, R, max_wav, (uint8_t*)out, out_ld);
-            break;
-        case RS_ENC_ALAW:
-            hipLaunchKernelGGL(resample_encode_kernel<RS_ENC_ALAW>, grid, block, lds, s, wav, ld, seg, table, L, M, R, max_wav, (uint8_t*)out, out_ld);
-            break;
-        default:
-            return -2;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    // gains == NULL runs the instantiation without the multiplication: the kernel as it was before the gain existed
+    return gains ? launch_encode<true>(wav, ld, seg, table, L, M, R, enc, max_wav, out, out_ld, gains, grid, lds, s)
+                 : launch_encode<false>(wav, ld, seg, table, L, M, R, enc, max_wav, out, out_ld, nullptr, grid, lds, s);
+}
+
+extern "C" int cmtts_launch_resample_encode(const float* wav, long ld, const ResampleSegment* seg, int N, const float* table, int L, int M, int R,
+                                            int enc, float max_wav, void* out, long out_ld, void* stream) {
+    return cmtts_launch_resample_encode_gain(wav, ld, seg, N, table, L, M, R, enc, max_wav, out, out_ld, nullptr, stream);
 }

@@ -1143,10 +1143,11 @@ def vocoder_infer_device(mels, vocoder, max_wav_value=32768.0):
 class _Resampler:
     """One (L, M) resampler of a vocoder: the float32 taps of cmtts_amd.resample.design_taps handed to cmtts_resampler_create."""
 
-    def __init__(self, lib, device, L, M):
+    def __init__(self, lib, device, L, M, identity=False):
         from . import resample as rs
         self.lib, self.L, self.M = lib, L, M
-        self.taps, self.half = rs.design_taps(L, M)
+        # identity (L = M = 1 only): the single tap 1.0 — y = x, what a gain at the native rate rides on without filtering anything
+        self.taps, self.half = (np.ones(1, np.float32), 0) if identity else rs.design_taps(L, M)
         self.R = rs.half_width(L, self.half)
         self._h = C.c_void_p()
         with torch.cuda.device(device):
@@ -1162,55 +1163,157 @@ class _Resampler:
         return -(-int(n) * self.L // self.M)
 
 
-def _output_format(vocoder, sample_rate, encoding):
+def _output_format(vocoder, sample_rate, encoding, force=False):
     """None for the native format (the vocoder's rate, "s16": the existing path, wrap included), else (resampler, encoding code,
-    torch dtype).  The filter of a rate is designed once per vocoder (cmtts_amd.resample.design_taps)."""
+    torch dtype).  The filter of a rate is designed once per vocoder (cmtts_amd.resample.design_taps).  force: the float path for the
+    native format too — what a gain rides on; at the native rate it is the L = M = 1 resampler with the single tap 1.0, which filters
+    nothing (the output is the encoding of fl32(g x); "s16" then saturates)."""
     from . import resample as rs
     if encoding not in rs.ENCODINGS:
         raise ValueError(f"encoding {encoding!r}: expected one of {sorted(rs.ENCODINGS)}")
     native = rs.NATIVE_RATE
     rate = native if sample_rate is None else int(sample_rate)
-    if rate == native and encoding == "s16":
+    if rate == native and encoding == "s16" and not force:
         return None
     L, M = rs.ratio(native, rate)
     cache = vocoder.__dict__.setdefault("_resamplers", {})
-    if (L, M) not in cache:
-        cache[(L, M)] = _Resampler(vocoder.lib, vocoder.device, L, M)
+    key = (L, M, "identity") if force and rate == native else (L, M)
+    if key not in cache:
+        cache[key] = _Resampler(vocoder.lib, vocoder.device, L, M, identity=len(key) == 3)
     dtype = {"f32": torch.float32, "s16": torch.int16, "mulaw": torch.uint8, "alaw": torch.uint8}[encoding]
-    return cache[(L, M)], rs.ENCODINGS[encoding], dtype
+    return cache[key], rs.ENCODINGS[encoding], dtype
 
 
-def _resample_encode(lib, rsm, wav, seg_tab, enc, dtype, max_wav_value, out_ld):
-    """cmtts_resample_encode on the current stream: wav fp32 [rows, ld] (device), seg_tab int32 [N, 5] (pinned host or device)."""
+def _resample_encode(lib, rsm, wav, seg_tab, enc, dtype, max_wav_value, out_ld, gains=None):
+    """cmtts_resample_encode on the current stream: wav fp32 [rows, ld] (device), seg_tab int32 [N, 5] (pinned host or device).
+    gains: fp32 [rows] (device), one per source row — cmtts_resample_encode_gain."""
     N = seg_tab.shape[0]
     out = torch.empty(N, out_ld, dtype=dtype, device=wav.device)
-    _lib.check(lib.cmtts_resample_encode(rsm._h, _ptr(wav), wav.shape[0], wav.shape[1], _ptr(seg_tab), N, enc, float(max_wav_value),
-                                         _ptr(out), out_ld, _stream()))
+    if gains is None:
+        _lib.check(lib.cmtts_resample_encode(rsm._h, _ptr(wav), wav.shape[0], wav.shape[1], _ptr(seg_tab), N, enc, float(max_wav_value),
+                                             _ptr(out), out_ld, _stream()))
+    else:
+        assert gains.dtype == torch.float32 and gains.is_contiguous() and gains.numel() == wav.shape[0]
+        _lib.check(lib.cmtts_resample_encode_gain(rsm._h, _ptr(wav), wav.shape[0], wav.shape[1], _ptr(seg_tab), N, enc,
+                                                  float(max_wav_value), _ptr(out), out_ld, _ptr(gains), _stream()))
+    return out
+
+
+# ----------------------------------------------------------------------------- loudness and output gain (DESIGN.md §3.5f)
+
+def _per_utterance(what, value, B):
+    """A number or [B] values -> float64 numpy [B]."""
+    v = np.asarray(value.detach().cpu().numpy() if torch.is_tensor(value) else value, dtype=np.float64)
+    if v.ndim == 0:
+        return np.full(B, float(v))
+    if v.shape != (B,):
+        raise ValueError(f"{what}: expected a number or {B} values, got shape {tuple(v.shape)}")
+    return v
+
+
+def _linear_gains(what, gain_db, B, device):
+    """gain_db (a number or [B]) -> fp32 [B] linear gains on the device: 10^(gain_db / 20) in float64, rounded once."""
+    g = _per_utterance(what, gain_db, B)
+    if not np.isfinite(g).all():
+        raise ValueError(f"{what}: gain_db must be finite")
+    return torch.from_numpy((10.0 ** (g / 20.0)).astype(np.float32)).to(device)
+
+
+def _measure_loudness(vocoder, wavs, lens, target=None, peak_ceiling_db=-1.0):
+    """cmtts_loudness_measure on the current stream: wavs fp32 [B, n] (device), lens valid samples per row, target None or float64 [B]
+    (NaN: measure only) -> stats fp32 [B, 4] on the device (L, sample peak, linear gain, gated blocks).  No synchronisation."""
+    from . import resample as rs
+    lib, dev = vocoder.lib, wavs.device
+    B, n = wavs.shape
+    n_valid = torch.tensor([int(v) for v in lens], dtype=torch.int32).to(dev)
+    tgt = None if target is None else torch.from_numpy(np.asarray(target, np.float32)).to(dev)
+    stats = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    nb = lib.cmtts_loudness_workspace_bytes(B, n, rs.NATIVE_RATE)
+    ws = vocoder._ws.get("loudness", max(nb, 1), dev)
+    _lib.check(lib.cmtts_loudness_measure(_ptr(wavs), B, n, _ptr(n_valid), rs.NATIVE_RATE, None if tgt is None else _ptr(tgt),
+                                          float(peak_ceiling_db), _ptr(stats), _ptr(ws), nb, _stream()))
+    return stats
+
+
+def _clip_lengths(lengths, B, n):
+    return [n] * B if lengths is None else [min(max(int(v), 0), n) for v in lengths]
+
+
+def _append_stats(stats, st, gains):
+    """One dict per utterance from the device stats [B, 4]; gains: the fixed gains applied instead of the measured ones, or None."""
+    st = st.cpu().numpy()
+    g = st[:, 2] if gains is None else gains.cpu().numpy()
+    for b, (L, pk, _, nblk) in enumerate(st):
+        stats.append({"lufs": float(L), "peak": float(pk), "gain_db": 20.0 * math.log10(float(g[b])), "blocks": int(nblk)})
+
+
+def vocoder_loudness(mels, vocoder, lengths=None):
+    """Integrated loudness (ITU-R BS.1770; the definition: cmtts_amd.loudness) of what vocoder_infer would deliver, measured on the
+    device: mels [B,80,T] -> float32 numpy [B, 4] = (L in LKFS, sample peak, 1.0, gated blocks) per utterance; `lengths` counts
+    samples as vocoder_infer's.  It only measures — the generator, then cmtts_loudness_measure: the way to calibrate a voice once and
+    pass a fixed gain_db afterwards (a stream cannot know its integrated loudness before it ends)."""
+    wavs = vocoder(mels).squeeze(1)
+    B, n = wavs.shape
+    with torch.cuda.device(wavs.device):
+        stats = _measure_loudness(vocoder, wavs, _clip_lengths(lengths, B, n))
+    out = stats.cpu().numpy()
+    check_async_error()
     return out
 
 
 def vocoder_infer(mels, vocoder, model_config=None, preprocess_config=None, lengths=None, max_wav_value=32768.0,
-                  sample_rate=None, encoding="s16"):
+                  sample_rate=None, encoding="s16", loudness=None, peak_ceiling_db=-1.0, gain_db=None, stats=None):
     """utils/model.py:187-205: mels [B,80,T] -> list of int16 numpy arrays trimmed to `lengths`.
     sample_rate / encoding: another output rate (8000, 16000, 24000, 32000, 44100, 48000) and / or "f32", "s16",
     "mulaw", "alaw" — resampled and encoded on the device by one cmtts_resample_encode after the unchanged generator; `lengths` still
     counts SOURCE samples, row b comes back with ceil(lengths[b] * L / M) samples of dtype float32 / int16 / uint8, and "s16" saturates.
-    The defaults (None or the native 22 050 Hz, "s16") are the reference's cast, wrap included."""
+    The defaults (None or the native 22 050 Hz, "s16") are the reference's cast, wrap included.
+    loudness / gain_db (give one, not both): a target in LUFS resp. a fixed gain in dB, a number or [B] values.
+    loudness measures every utterance's integrated loudness (BS.1770, over its `lengths` samples) on the device after the generator and
+    scales it to the target, with the SAMPLE peak kept at or under peak_ceiling_db dBFS (no true-peak oversampling: a resampled wave can
+    still overshoot between samples, which the saturating encoders absorb); NaN leaves that utterance alone.  Either one takes the
+    float path for every format — the gain is one fp32 multiplication per source sample in cmtts_resample_encode_gain's staging, the
+    native rate runs the L = M = 1 resampler with the single tap 1.0 (no filtering: the encoding of fl32(g x)) and "s16" saturates.  stats: a list that receives one dict per utterance: "lufs" (before
+    the gain; -inf for silence), "peak", "gain_db" (passing these as gain_db reproduces the output bit for bit), "blocks"."""
     if preprocess_config is not None:
         max_wav_value = preprocess_config["preprocessing"]["audio"]["max_wav_value"]
-    fmt = _output_format(vocoder, sample_rate, encoding)
+    if loudness is not None and gain_db is not None:
+        raise ValueError("vocoder_infer: give loudness (a target in LUFS) or gain_db (a fixed gain), not both")
+    if stats is not None and not isinstance(stats, list):
+        raise ValueError("vocoder_infer: stats must be a list")
+    leveled = loudness is not None or gain_db is not None
+    fmt = _output_format(vocoder, sample_rate, encoding, force=leveled)
     if fmt is not None:
         rsm, enc, dtype = fmt
         wavs = vocoder(mels).squeeze(1)
         B, n = wavs.shape
-        lens = [n] * B if lengths is None else [min(max(int(v), 0), n) for v in lengths]
+        lens = _clip_lengths(lengths, B, n)
         tab = torch.tensor([(b, 0, 0, rsm.out_len(lens[b]), lens[b]) for b in range(B)], dtype=torch.int32).pin_memory()
         with torch.cuda.device(wavs.device):
-            out = _resample_encode(vocoder.lib, rsm, wavs, tab, enc, dtype, max_wav_value, max(rsm.out_len(n), 1))
+            gains = st = None
+            if loudness is not None:
+                target = _per_utterance("vocoder_infer: loudness", loudness, B)
+                st = _measure_loudness(vocoder, wavs, lens, target, peak_ceiling_db)
+                gains = st[:, 2].contiguous()
+            elif gain_db is not None:
+                gains = _linear_gains("vocoder_infer: gain_db", gain_db, B, wavs.device)
+            if stats is not None and st is None:
+                st = _measure_loudness(vocoder, wavs, lens)
+            out = _resample_encode(vocoder.lib, rsm, wavs, tab, enc, dtype, max_wav_value, max(rsm.out_len(n), 1), gains)
         arr = out.cpu().numpy()          # synchronises: the pinned table is free again
         check_async_error()
+        if stats is not None:
+            _append_stats(stats, st, None if gain_db is None else gains)
         return [arr[b, : rsm.out_len(lens[b])] for b in range(B)]
-    pcm = vocoder_infer_device(mels, vocoder, max_wav_value)
+    if stats is not None:          # the native format, measured but not scaled: vocoder_infer_device's two calls around the measurement
+        wavs = vocoder(mels).squeeze(1)
+        pcm = torch.empty(wavs.shape, dtype=torch.int16, device=wavs.device)
+        with torch.cuda.device(wavs.device):
+            st = _measure_loudness(vocoder, wavs, _clip_lengths(lengths, *wavs.shape))
+            _lib.check(vocoder.lib.cmtts_wav_to_int16(_ptr(wavs), _ptr(pcm), wavs.numel(), float(max_wav_value), _stream()))
+        _append_stats(stats, st, None)
+    else:
+        pcm = vocoder_infer_device(mels, vocoder, max_wav_value)
     out = [w for w in pcm.cpu().numpy()]
     check_async_error()          # the D2H copy synchronised: a timeout in the launches that produced `mels` is raised here
     if lengths is not None:
@@ -1280,7 +1383,7 @@ def plan_stream_windows(T, mel_lens, chunk_frames=STREAM_CHUNK_FRAMES, halo=13):
 
 
 def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_FRAMES, max_wav_value=32768.0,
-                         sample_rate=None, encoding="s16"):
+                         sample_rate=None, encoding="s16", gain_db=None, loudness=None):
     """vocoder_infer, streamed: mels [B,80,T] -> a generator of (utterance, sample_offset, pcm int16 numpy, is_last), round by round
     (plan_stream_windows; lengths = mel FRAMES per utterance, default T — vocoder_infer's `lengths` count samples).  Concatenated per
     utterance the chunks are vocoder_infer(mels, lengths=mel_len * hop)'s output: bitwise with the direct fp32 form ("winograd" 0),
@@ -1289,12 +1392,20 @@ def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_
     sample_rate / encoding (vocoder_infer): the windows reach one frame further (halo H + 1), each round's last layer
     writes fp32 rows with one frame of margin (cmtts_vocoder_forward_windows_f32) and one cmtts_resample_encode turns the round's cores
     into chunks of the output format; offsets then count OUTPUT samples, an utterance's chunks concatenate to
-    ceil(mel_len * hop * L / M) samples and are bitwise vocoder_infer(..., sample_rate, encoding)'s under the same condition."""
+    ceil(mel_len * hop * L / M) samples and are bitwise vocoder_infer(..., sample_rate, encoding)'s under the same condition.
+    gain_db (vocoder_infer): a fixed gain per utterance, a number or [B] values — each round gathers the utterance
+    gains to its window rows on the device and the gain rides on the round's cmtts_resample_encode_gain (the float path for the native
+    format too); one multiplication per source sample, so the chunks stay bitwise vocoder_infer(..., gain_db=...)'s.  A loudness
+    TARGET is not available on a stream (ValueError): measure with vocoder_loudness and pass gain_db."""
+    if loudness is not None:
+        raise ValueError("vocoder_infer_stream: integrated loudness needs the whole utterance, which a stream does not have when its "
+                         "first chunk leaves: calibrate the voice with vocoder_loudness and pass gain_db")
     vocoder._require()
     lib, dev = vocoder.lib, vocoder.device
-    fmt = _output_format(vocoder, sample_rate, encoding)
+    fmt = _output_format(vocoder, sample_rate, encoding, force=gain_db is not None)
     x = _f32(mels, dev)
     B, M, T = x.shape
+    gains = None if gain_db is None else _linear_gains("vocoder_infer_stream: gain_db", gain_db, B, dev)
     lens = [T] * B if lengths is None else [int(n) for n in lengths]
     if len(lens) != B:
         raise ValueError(f"vocoder_infer_stream: {len(lens)} lengths for {B} mels")
@@ -1330,7 +1441,9 @@ def vocoder_infer_stream(mels, vocoder, lengths=None, chunk_frames=STREAM_CHUNK_
                 segs = [(n, max(start + off - 1, start) * hop, rsm.out_len((start + off) * hop), rsm.out_len((start + off + cl) * hop),
                          lens[b] * hop) for n, (b, start, off, cl) in enumerate(r.windows)]
                 seg_tab = torch.tensor(segs, dtype=torch.int32).pin_memory()
-                pcm = _resample_encode(lib, rsm, rows, seg_tab, enc, dtype, max_wav_value, max(m1 - m0 for _, _, m0, m1, _ in segs))
+                row_gains = None if gains is None else gains[torch.tensor([w[0] for w in r.windows], device=dev)]
+                pcm = _resample_encode(lib, rsm, rows, seg_tab, enc, dtype, max_wav_value, max(m1 - m0 for _, _, m0, m1, _ in segs),
+                                       row_gains)
                 tab = (tab, seg_tab, segs)
             ready = torch.cuda.Event()
             ready.record(comp)
@@ -1390,7 +1503,7 @@ def phoneme_marks(out, T=None, sample_rate=None, vocoder=None):
 def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=None, speakers=None, n_steps=4, noise=None,
                       chunk_frames=STREAM_CHUNK_FRAMES, generator=None, max_wav_value=32768.0,
                       p_control=1.0, e_control=1.0, d_control=1.0, seeds=None, sample_rate=None, encoding="s16",
-                      target_frames=None, segments=None, on_marks=None):
+                      target_frames=None, segments=None, on_marks=None, gain_db=None, loudness=None):
     """Text -> streamed PCM: the duration net and the T-step sampler exactly as CMTotalTTSSynthesize.synthesize runs them (noise
     [n_noise, B, 1, T, 80] drawn as x0 = randn, then randn_like(x0) per further step, unless given), then vocoder_infer_stream on
     the mels trimmed to their predicted lengths.  Yields (utterance, sample_offset, pcm int16 numpy, is_last).
@@ -1400,7 +1513,11 @@ def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=
     target_frames / segments: duration targets (DurationPitchSpeakerNet.forward): utterance b's chunks then concatenate to exactly
     out_len(target * hop) samples.
     on_marks: a callable that receives phoneme_marks(...) as int32 numpy [B, L, 4] once, before the first chunk is handed out, in the
-    stream's own output rate — the scale of the chunk offsets.  What the generator yields does not change."""
+    stream's own output rate — the scale of the chunk offsets.  What the generator yields does not change.
+    gain_db: a fixed gain per utterance (vocoder_infer_stream); loudness= is refused as it is there."""
+    if loudness is not None:
+        raise ValueError("synthesize_stream: integrated loudness needs the whole utterance, which a stream does not have when its "
+                         "first chunk leaves: calibrate the voice with vocoder_loudness and pass gain_db")
     if seeds is not None and noise is not None:
         raise ValueError("synthesize_stream: give noise or seeds, not both")
     if on_marks is not None and not callable(on_marks):
@@ -1420,7 +1537,7 @@ def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=
     if on_marks is not None:
         on_marks(phoneme_marks(out, sample_rate=sample_rate, vocoder=vocoder).cpu().numpy())
     yield from vocoder_infer_stream(mel.transpose(1, 2), vocoder, mel_lens, chunk_frames, max_wav_value, sample_rate=sample_rate,
-                                    encoding=encoding)
+                                    encoding=encoding, gain_db=gain_db)
 
 
 def synth_samples(args, targets, predictions, vocoder, model_config, preprocess_config, path, diffusion=None):

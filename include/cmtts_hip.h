@@ -68,6 +68,7 @@ const char* cmtts_version(void);
  * signature changes, so the number stays; a host detects it by looking the symbol up (dlsym).  Likewise the resampler
  * (cmtts_resampler_*, cmtts_resample_encode) and cmtts_vocoder_forward_windows_f32: entry points only, still 8; and the duration
  * targets (cmtts_set_duration_targets, a new struct) with cmtts_phoneme_marks: entry points only, still 8.
+ * Likewise the loudness measurement (cmtts_loudness_*) and cmtts_resample_encode_gain: entry points only, still 8.
  * A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
  * against before it passes a struct (cmtts_amd/_lib.py does at load time). */
 #define CMTTS_ABI_VERSION 8
@@ -428,6 +429,32 @@ int cmtts_resample_encode(cmtts_resampler* r, const float* wav, int rows, int64_
                           float max_wav_value, void* out, int64_t out_ld, void* stream);
 int cmtts_vocoder_forward_windows_f32(cmtts_vocoder* v, const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, int core,
                                       int margin_frames, float* wav_rows, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- loudness measurement and output gain (the definition in executable form: cmtts_amd/loudness.py).
+ * Integrated loudness by ITU-R BS.1770 of mono fp32 rows: K-weighting (two biquads derived for `fs` by the bilinear transform; the
+ * BS.1770-4 table at 48 kHz), 0.4 s blocks with a 0.1 s hop that lie wholly inside [0, n), the absolute gate at -70 LKFS and the relative
+ * gate 10 LU under the absolutely gated mean.  A row shorter than one block is one block [0, n) under the absolute gate alone; an empty
+ * row, or one no block of which passes, has L = -inf.  The peak is the SAMPLE peak max |x[0 .. n)|: no true-peak oversampling.
+ * fs % 10 == 0 and 8000 <= fs <= 48000, else CMTTS_E_INVALID.
+ * cmtts_loudness_coefficients: host only, never touches the GPU: out10 = b0 b1 b2 a1 a2 of the shelf, then of the high-pass, in double.
+ * cmtts_loudness_measure: wav fp32 [rows][ld] (device); n_valid int32 [rows] (device or page-locked host memory, read by the kernels on
+ * `stream`: keep it unchanged until the call's work has completed; values are clamped to [0, ld]); whatever the rows hold at or beyond
+ * n_valid is never used, and a row's result does not depend on the other rows.  target_lufs fp32 [rows] (device) or NULL; ceiling_db: the
+ * sample-peak ceiling in dBFS (not NaN).  stats fp32 [rows][4] (device) = (L in LKFS, sample peak, linear gain, number of gated blocks):
+ * gain = 10^((target - L) / 20), lowered to 10^(ceiling_db / 20) / peak where peak * gain would exceed the ceiling, and exactly 1 when
+ * target_lufs is NULL, the row's target is NaN, L = -inf or the peak is 0 (measure only).  Two launches on `stream`, no allocation, no host
+ * synchronisation.  ws: cmtts_loudness_workspace_bytes(rows, ld, fs) bytes (0 for arguments the measurement rejects).  Null pointers, rows
+ * or ld < 1, rows > 65535, a bad fs, a NaN ceiling or a workspace that is too small: CMTTS_E_INVALID, checked before any launch.
+ * cmtts_resample_encode_gain: cmtts_resample_encode with gains fp32 [rows] (device), indexed by a segment's SOURCE row: every source
+ * sample x is replaced by fl32(gains[row] * x) as it is staged — one multiplication per source sample, so pieces stay BITWISE the whole.
+ * gains == NULL is cmtts_resample_encode itself.  A ceiling bounds the source samples; the resampled wave can still overshoot between
+ * them, which the saturating encoders absorb. */
+int cmtts_loudness_coefficients(int fs, double* out10);
+int64_t cmtts_loudness_workspace_bytes(int rows, int64_t ld, int fs);
+int cmtts_loudness_measure(const float* wav, int rows, int64_t ld, const int32_t* n_valid, int fs, const float* target_lufs, float ceiling_db,
+                           float* stats, void* ws, size_t ws_bytes, void* stream);
+int cmtts_resample_encode_gain(cmtts_resampler* r, const float* wav, int rows, int64_t ld, const int32_t* segments, int N, int encoding,
+                               float max_wav_value, void* out, int64_t out_ld, const float* gains, void* stream);
 
 /* ---- measurement hook (no reference counterpart; the reference's only perf tooling is the
  * wall-clock Timer of p_rtf_cm.py:64-108): HIP events recorded on the launch stream around every
