@@ -1,5 +1,5 @@
 // C ABI of the MI355X-native CM-TTS inference hot path (include/cmtts_hip.h): the entry points, workspace carving and the
-// host-side launch sequences (weight import: import.hip; handles: model.h).  No allocation and no
+// host-side launch sequences (weight import: import.hip; handles: model.h; the vocoder: vocoder.hip, shared helpers: launch.h).  No allocation and no
 // host synchronisation after cmtts_finalize(); everything is enqueued on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -15,8 +15,8 @@
 
 #include "../../include/cmtts_hip.h"
 #include "model.h"
+#include "launch.h"
 #include "internal_hooks.h"
-#include "conv_args.h"
 #include "kernels.h"
 #include "resblock_args.h"
 #include "persist_args.h"
@@ -30,15 +30,13 @@
 #include "loudness.h"
 #include "noise_philox.h"
 
-
 static thread_local std::string g_err;
 int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
 
-namespace {
-
+// What launch.h declares, for this unit and vocoder.hip
 ConvArgs conv_args(const PackedConv& w, const float* X, int Tin, int ldx, long x_bs, float* Y, int ldy, long y_bs, int N) {
     ConvArgs a;
     memset(&a, 0, sizeof(a));
@@ -63,18 +61,57 @@ int launch(const ConvArgs& a, int epi, int nbatch, hipStream_t s) {
     return 0;
 }
 
-struct Carver {
-    char* base;
-    size_t off = 0;
-    explicit Carver(void* b) : base((char*)b) {}
-    template <class T>
-    T* take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = (T*)(base + off);
-        off += n * sizeof(T);
-        return p;
+int knob_set(const Knob* tab, size_t n, const char* name, int value, bool* found) {
+    for (size_t i = 0; i < n; ++i)
+        if (!strcmp(name, tab[i].name)) {
+            *found = true;
+            const int prev = *tab[i].var;
+            if (value >= tab[i].lo && value <= tab[i].hi) *tab[i].var = value;
+            return prev;
+        }
+    *found = false;
+    return 0;
+}
+
+// Independent branches of the text side (duration / energy predictors, ...) are short launches that cannot fill the chip:
+// a branch runs on a side stream forked from and joined back into the caller's stream with events, so the two overlap.
+// One side stream per caller stream (callers that run bucket groups on several streams keep their concurrency).
+static int g_branch_streams = 1;
+static std::vector<SideStream> g_sides;
+SideStream* side_for(hipStream_t s) {
+    if (!g_branch_streams) return nullptr;
+    if (g_sides.capacity() < 16) g_sides.reserve(16);      // callers keep SideStream pointers across nested side_for() calls: never reallocate (only grows while empty)
+    for (auto& x : g_sides)
+        if (x.user == s) return &x;
+    if (g_sides.size() >= 16) return nullptr;          // more caller streams than that: branches run in line
+    SideStream x{s, nullptr, nullptr, nullptr};
+    // (round 4: a LOW-priority branch stream was tried — the chip-filling conditioner factor GEMM stretches the latency-bound kernels of the
+    // main chain — headline 12.66 ms either way, and the ragged shard's set-aside sampler, which lives on this stream, starves: 18 -> 28 ms)
+    if (hipStreamCreateWithFlags(&x.side, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&x.join, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
     }
-};
+    g_sides.push_back(x);
+    return &g_sides.back();
+}
+// The vocoder's third stream and chain events, created on first use only: HIP maps streams onto a handful of hardware
+// queues in creation order, and idle extra streams made four caller streams (bucket groups) collide (25 -> 39 ms).
+bool side2_ready(SideStream* ss) {
+    if (ss->side2) return true;
+    if (hipStreamCreateWithFlags(&ss->side2, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&ss->join2, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&ss->done0, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&ss->done1, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        ss->side2 = nullptr;
+        return false;
+    }
+    return true;
+}
+
+namespace {
 
 // Optional HIP-event instrumentation of the dominant kernel (the gated k=3 conv of the denoiser
 // residual block), recorded on the launch stream: bench.py's live roofline figure.
@@ -99,23 +136,10 @@ int g_step_cache = 1;           // cmtts_sample: reuse the timestep-only part of
 int g_persist_wino = 3;         // fp32 persistent denoiser: the k = 3 conv in a Winograd form (NOT bitwise the direct form): 3 = F(4,3), the 8-wave WINO == 2 instances
                                 // of denoiser_persist.hip (default since round 5: half of the conv's MFMAs), 1 = F(2,3), the 8-wave WINO == 1 instances (2/3), 0 = direct
                                 // (2 was round 5's one-wave-per-SIMD F(2,3) stack — same bits as 1, measured 4-10 % slower, out of the build since round 6: tools/attic/ — and runs as 1)
-int g_voc_wino = 1;             // fp32 HiFi-GAN, C >= 128: ResBlock convs in their Winograd form (conv_xlw_kernel; NOT bitwise the direct form): 0 never, 1 launches of >= 1024 column tiles, 2 always (tests)
-int g_voc_wino64_k = 7;          // smallest kernel size of the C = 64 stage that takes the two-launch Winograd form (measurement switch voc_wino64_k)
-int g_voc_wino43 = 1;           // fp32 HiFi-GAN: the convs of the Winograd path in the F(4,3) form (conv_xlq_kernel) instead of F(2,3) tap groups (measurement switch; 1 = dilation 1 and 3 everywhere + dilation 5 at C = 256 or k = 3 (default), 2 = only dilation 1, 3 = every dilation)
-int g_voc_qpair = 1;            // fp32 HiFi-GAN, k = 3 pairs at C = 64 / 128 of the Winograd path: both convs F(4,3) in ONE launch, xt on the CU (conv_xlq_pair.hip; NOT bitwise the two conv_xlq launches: the quads of its conv1 start one frame earlier): 0 never, 1 launches of >= 1024 column tiles, 2 always (tests)
-int g_voc_wino64 = 1;           // fp32 HiFi-GAN, C = 64, k >= 7: two Winograd launches per pair instead of the pair kernel (measurement switch)
-int g_voc_pair3 = 1;            // fp16x3 HiFi-GAN, C <= 128: ResBlock pair as ONE X-resident launch (resblock_pair16x3.hip; same bits); 0 = two conv16 launches per pair
-int g_voc_pairw = 1;            // 16-bit HiFi-GAN, C = 128: ResBlock pair as ONE launch with one in-place LDS image, two workgroups per CU (resblock_pairw16.hip; same bits); 0 = two conv_xl16 launches
-int g_voc_pair128 = 1;          // 16-bit HiFi-GAN, C = 128: pair kernel (1) or two conv_xl16 launches (0); same bits
-int g_voc_rb16 = 1;             // 16-bit HiFi-GAN, C <= 64: a whole ResBlock (three pairs) per launch (same bits); 0 = one launch per pair
-int g_voc_upsT = 1;             // HiFi-GAN upsamplers: all phases of a ConvTranspose1d in one X-resident launch (same bits); 0 = generic kernel, one z per phase
-int g_voc_xl16 = 1;             // 16-bit HiFi-GAN convs at C >= 128 on the X-resident conv_xl16 kernel (same bits); 0 = chunked conv_mfma16 kernel
 int g_pred_xl = 1;              // frame-level 256 -> 256 predictor convs on the X-resident conv_xl kernel (bitwise equal); 0 = generic kernel
 int g_pred_head = 1;            // predictors: last LayerNorm + linear head as one launch (ln_linear_kernel); 0 = layernorm_ct + chan_linear
 int g_text_xres = 7;            // FFT blocks, bit mask: 1 = LayerNorm1 + in-projection in one X-resident launch, 2 = out-projection on that kernel (round 4: its 32-column instance, default on), 4 = LayerNorm2 as the prologue of the FFN conv; 0 = separate LayerNorm launches
 int g_attn_fused = 1;           // FFT-block attention as QKV projection + ONE fused kernel (attention.hip; key-chunked with an online softmax above L = 192): 0 = three-launch path
-int g_voc_xl = 1;               // HiFi-GAN ResBlock convs of the C >= 128 stages through the X-resident kernel (conv_xl): 0 never, 1 yes
-int g_voc_pair = 1;             // HiFi-GAN ResBlock pairs of the C <= 64 stages as one launch (resblock_pair{,16}.hip): 0 never, 1 where it pays, 2 always
 int g_qkv_nt = 0;              // internal switch "qkv_nt": conv_xres tile width of the in-projection (0 = launcher's rule, 1, 3) — measurements
 int g_stats_mlp = 1;           // round 6: cwt_stats_layers as one launch (kernels.hip: stats_mlp_kernel; same bits); 0 = three dense_small launches
 int g_cwt_in_phoneme = 1;      // round 4: the pitch predictor's input projection applied before the length regulator (same bits); 0 = over the frames
@@ -209,49 +233,6 @@ int persist_launched(hipStream_t s, int blocks) {
     return 0;
 }
 
-// Independent branches of the text side (duration / energy predictors, ...) are short launches that cannot fill the chip:
-// a branch runs on a side stream forked from and joined back into the caller's stream with events, so the two overlap.
-// One side stream per caller stream (callers that run bucket groups on several streams keep their concurrency).
-int g_branch_streams = 1;
-struct SideStream {
-    hipStream_t user, side;
-    hipEvent_t fork, join;
-    hipStream_t side2 = nullptr;                      // second side stream + chain events: the three ResBlocks of an MRF stage
-    hipEvent_t join2 = nullptr, done0 = nullptr, done1 = nullptr;
-};
-std::vector<SideStream> g_sides;
-SideStream* side_for(hipStream_t s) {
-    if (!g_branch_streams) return nullptr;
-    if (g_sides.capacity() < 16) g_sides.reserve(16);      // callers keep SideStream pointers across nested side_for() calls: never reallocate (only grows while empty)
-    for (auto& x : g_sides)
-        if (x.user == s) return &x;
-    if (g_sides.size() >= 16) return nullptr;          // more caller streams than that: branches run in line
-    SideStream x{s, nullptr, nullptr, nullptr};
-    // (round 4: a LOW-priority branch stream was tried — the chip-filling conditioner factor GEMM stretches the latency-bound kernels of the
-    // main chain — headline 12.66 ms either way, and the ragged shard's set-aside sampler, which lives on this stream, starves: 18 -> 28 ms)
-    if (hipStreamCreateWithFlags(&x.side, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x.join, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    g_sides.push_back(x);
-    return &g_sides.back();
-}
-// The vocoder's third stream and chain events, created on first use only: HIP maps streams onto a handful of hardware
-// queues in creation order, and idle extra streams made four caller streams (bucket groups) collide (25 -> 39 ms).
-bool side2_ready(SideStream* ss) {
-    if (ss->side2) return true;
-    if (hipStreamCreateWithFlags(&ss->side2, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&ss->join2, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ss->done0, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ss->done1, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        ss->side2 = nullptr;
-        return false;
-    }
-    return true;
-}
 int branch_fork(SideStream* ss) {       // work queued on ss->side after this sees everything queued on ss->user so far
     HIPCHK(hipEventRecord(ss->fork, ss->user));
     HIPCHK(hipStreamWaitEvent(ss->side, ss->fork, 0));
@@ -1810,486 +1791,6 @@ int cmtts_sample_ragged(cmtts_model* m, const cmtts_sample_group* groups, int n_
     return 0;
 }
 
-// ------------------------------------------------------------------------------ vocoder
-int cmtts_vocoder_create(cmtts_vocoder** out) {
-    if (!out) return fail(CMTTS_E_INVALID, "cmtts_vocoder_create: null argument");
-    *out = new cmtts_vocoder();
-    return 0;
-}
-int cmtts_vocoder_set_tensor(cmtts_vocoder* v, const char* name, const float* host_data, const int64_t* shape, int ndim) {
-    if (!v || v->finalized) return fail(CMTTS_E_INVALID, "cmtts_vocoder_set_tensor: null or finalized");
-    return set_tensor(v->host, name, host_data, shape, ndim);
-}
-int cmtts_vocoder_finalize(cmtts_vocoder* v) {
-    if (!v || v->finalized) return fail(CMTTS_E_INVALID, "cmtts_vocoder_finalize: null or finalized");
-    const int r = finalize_vocoder(v);
-    if (r != 0) v->al.release();
-    return r;
-}
-void cmtts_vocoder_destroy(cmtts_vocoder* v) {
-    if (!v) return;
-    v->al.release();
-    delete v;
-}
-// Row padding of the stage buffers (floats).  Power-of-two row strides were suspected of HBM channel
-// camping; padding by 256 B or 4 KB + 128 B changed the vocoder time by < 2 %, so rows stay dense.
-static int voc_row_pad() {      // extra floats per row of the stage buffers (experiment switch CMTTS_VOC_PAD: power-of-two row strides put every channel row of a column block on the same HBM channel)
-    static const int p = [] { const char* e = getenv("CMTTS_VOC_PAD"); const int v = e ? atoi(e) : 0; return v > 0 && v <= 4096 ? v & ~3 : 0; }();
-    return p;
-}
-// The three ResBlocks of an MRF stage are independent until their sum: they run on three streams (own xt / residual
-// buffers, + 4 stage buffers of workspace).  Small batches, whose convs cannot fill the chip (stage 2 has B*T/2
-// workgroups), gain most — one 150-frame utterance 4.1 -> 2.7 ms — and 32 x 512 frames still 1 % (tails of one ResBlock's
-// launches under the next one's).  Above this many mel frames per call the extra workspace (4 x 32 KB per frame) is not
-// spent and the ResBlocks run in line.
-constexpr long VOC_PAR_FRAMES = 65536;
-size_t cmtts_vocoder_workspace_bytes(const cmtts_vocoder* v, int B, int T) {
-    (void)v;
-    // five stage buffers of B * max_i(C_i * T_i) floats: C_i*T_i = T * {512, 2048, 8192, 8192, 8192}
-    // (rows are padded by VOC_ROW_PAD floats; at most 512 rows per utterance)
-    // + four more (xt / running residual of the second and third ResBlock) when the batch is small enough for the three
-    // ResBlocks of a stage to run side by side (VOC_PAR_FRAMES)
-    const int nb = (long)B * T <= VOC_PAR_FRAMES ? 9 : 5;
-    return (size_t)nb * (((size_t)B * T * 8192 + (size_t)B * 512 * voc_row_pad()) * sizeof(float) + 256) + 256;
-}
-// The generator up to (not including) its last layer: mel_ct [B,80,T] -> the last MRF sum [B][ch][ld] with Ti = 256 T valid columns
-// (*x_out, still to be divided by the ResBlock count; ld = Ti + row pad), in the workspace of cmtts_vocoder_workspace_bytes(v, B, T).
-// Shared by cmtts_vocoder_forward (whole mels) and cmtts_vocoder_forward_windows (a batch of mel windows).
-static int vocoder_generator(cmtts_vocoder* v, const float* mel_ct, int B, int T, void* ws, hipStream_t s, const float** x_out,
-                             int* ch_out, int* Ti_out, int* ld_out) {
-    Carver cv(ws);
-    const int P = voc_row_pad();
-    const size_t nbuf = (size_t)B * T * 8192 + (size_t)B * 512 * P;
-    float* bufA = cv.take<float>(nbuf);   // stage input
-    float* bufU = cv.take<float>(nbuf);   // upsampled
-    float* bufT = cv.take<float>(nbuf);   // xt
-    float* bufR = cv.take<float>(nbuf);   // running residual inside a ResBlock
-    float* bufS = cv.take<float>(nbuf);   // MRF sum
-    SideStream* ss = (long)B * T <= VOC_PAR_FRAMES ? side_for(s) : nullptr;
-    if (ss && !side2_ready(ss)) ss = nullptr;
-    float *bufTj[3] = {bufT, bufT, bufT}, *bufRj[3] = {bufR, bufR, bufR};
-    hipStream_t sj[3] = {s, s, s};
-    if (ss) {   // own xt / residual buffers and streams for the second and third ResBlock
-        for (int j = 1; j < 3; ++j) { bufTj[j] = cv.take<float>(nbuf); bufRj[j] = cv.take<float>(nbuf); }
-        sj[1] = ss->side; sj[2] = ss->side2;
-    }
-    {   // conv_pre (hifigan/models.py:150)
-        ConvArgs a = conv_args(v->conv_pre, mel_ct, T, T, (long)80 * T, bufA, T + P, (long)512 * (T + P), T);
-        CHK(launch(a, EPI_PLAIN, B, s));
-    }
-    int Ti = T, ch = 512;
-    for (int i = 0; i < 4; ++i) {
-        const int st = v->up_rate[i], K = v->up_kernel[i], pd = (K - st) / 2, co = ch / 2, To = Ti * st;
-        {   // x = ups[i](leaky_relu(x, 0.1)) as `st` polyphase sub-convolutions (hifigan/models.py:152-153)
-            const PackedConv& U = v->ups[i];
-            int rt = -2;
-            if (v->ups16 && v->precision >= 1 && v->precision <= 3 && v->ups_f16[i][v->precision - 1] && K == 2 * st)
-                // 16-bit modes: the upsamplers' operands are 16-bit too (since round 2; the oracle's operands16 modes follow); fp16x3 (round 3):
-                // (hi, lo) operand pairs like the ResBlock convs
-                rt = cmtts_launch_convT16(bufA, bufU, v->ups_f16[i][v->precision - 1], U.bias, (long)ch * (Ti + P), (long)co * (To + P), B, ch,
-                                          co, Ti, To, Ti + P, To + P, st, i > 0 ? 3.0f : 1.0f, 0.1f, v->precision, (void*)s);
-            if (rt == -3) return fail(CMTTS_E_HIP, "convT16 launch failed");
-            if (rt != 0 && g_voc_upsT && v->ups_f[i] && K == 2 * st)      // all phases in one X-resident launch (same bits)
-                rt = cmtts_launch_convT(bufA, bufU, v->ups_f[i], U.bias, (long)ch * (Ti + P), (long)co * (To + P), B, ch, co, Ti, To,
-                                        Ti + P, To + P, st, i > 0 ? 3.0f : 1.0f, 0.1f, (void*)s);
-            if (rt == -3) return fail(CMTTS_E_HIP, "convT launch failed");
-            if (rt != 0) {
-            ConvArgs a = conv_args(U, bufA, Ti, Ti + P, (long)ch * (Ti + P), bufU, To + P, (long)co * (To + P), Ti + 1);
-            a.dil = -1; a.pad = 0;
-            a.zdiv = st; a.a_zs0 = 0; a.a_zs1 = U.phase_stride; a.x_zs0 = (long)ch * (Ti + P); a.x_zs1 = 0;
-            a.pre_slope = 0.1f;
-            a.pre_div = i > 0 ? 3.0f : 1.0f;     // x = xs / num_kernels of the previous stage (:160)
-            ConvOut& o = a.out[0];
-            o.Tout = To; o.ostride = st; o.ooff_base = -pd; o.ooff_mul = 1; o.y_zs0 = (long)co * (To + P); o.y_zs1 = 0;
-            CHK(launch(a, EPI_PLAIN, B * st, s));
-            }
-        }
-        const int ld = To + P;               // row stride: not a power of two (HBM channel spread)
-        const long cs = (long)co * ld;
-        if (ss) {   // the three chains see the upsampled input
-            HIPCHK(hipEventRecord(ss->fork, s));
-            HIPCHK(hipStreamWaitEvent(ss->side, ss->fork, 0));
-            HIPCHK(hipStreamWaitEvent(ss->side2, ss->fork, 0));
-        }
-        for (int j = 0; j < 3; ++j) {          // MRF: three ResBlocks on the same input (:154-159)
-            const int r = i * 3 + j, rk = v->rb_kernel[j];
-            hipStream_t q = sj[j];
-            float *bT = bufTj[j], *bR = bufRj[j];
-            const float* xr = bufU;
-            static const char* rb_only = getenv("CMTTS_RB16_ONLY");      // debugging aid: "C,k" restricts the fused ResBlock to one shape
-            int rbC = 0, rbK = 0;
-            const bool rb_sel = !rb_only || (sscanf(rb_only, "%d,%d", &rbC, &rbK) == 2 && rbC == co && rbK == rk);
-            // measured per ResBlock (bf16, 32 x 512 frames): C = 32: 0.51 / 0.83 / 1.10 ms (k = 3 / 7 / 11) against 1.21 / 1.30 / 1.40 for three
-            // pair launches; C = 64 (8 waves, one 118-KB workgroup per CU): 0.76 / 1.31 / 1.91 against 1.15 / 1.40 / 1.66 — at k = 11 the halo
-            // recompute (+45 % MFMAs) costs more than the four tensor passes saved (g_voc_rb16 == 2: the fused form always)
-            const bool rb_pays = co == 32 || rk <= 7 || g_voc_rb16 == 2;
-            if (g_voc_rb16 && rb_pays && rb_sel && (v->precision == 1 || v->precision == 2) && co <= 64 && v->c1f[r][0][v->precision - 1]) {
-                // narrow stages, 16-bit operands: the WHOLE ResBlock (three pairs) in one launch — x in, MRF sum out: 2 tensor
-                // passes instead of 6 (resblock16_kernel; bitwise equal to three pair launches)
-                const void *w1[3], *w2[3];
-                const float *bb1[3], *bb2[3];
-                for (int mi = 0; mi < 3; ++mi) {
-                    w1[mi] = v->c1f[r][mi][v->precision - 1]; w2[mi] = v->c2f[r][mi][v->precision - 1];
-                    bb1[mi] = v->c1[r][mi].bias; bb2[mi] = v->c2[r][mi].bias;
-                }
-                if (ss && j > 0) HIPCHK(hipStreamWaitEvent(q, j == 1 ? ss->done0 : ss->done1, 0));     // MRF sum in ResBlock order
-                const int rrc = cmtts_launch_resblock16(xr, bufS, w1, w2, bb1, bb2, cs, B, co, To, ld, rk, j > 0, 0.1f, v->precision, (void*)q);
-                if (rrc == -3) return fail(CMTTS_E_HIP, "resblock16 launch failed");
-                if (rrc == 0) {
-                    if (ss && j < 2) HIPCHK(hipEventRecord(j == 0 ? ss->done0 : ss->done1, q));
-                    continue;
-                }
-            }
-            // narrow stages: conv1 -> LeakyReLU -> conv2 -> + x of a pair in ONE launch, xt never leaves the CU
-            // (resblock_pair.hip; the pair's output must not alias its input, so the chain ping-pongs bR / bT)
-            // 16-bit operands: with the weight ring issued by hand (resblock_pair16.hip: the compiler had sunk every fragment load
-            // next to its use) the pair kernel wins for every (C, k): 0.37-0.55 ms per pair against 0.60-0.64 for two launches
-            // (profiles/r02_vocoder_bf16.md)
-            const bool pair16_pays = true;
-            // 16-bit, C = 128 (round 2): the pair as one 8-wave workgroup with both images in LDS (151 KB) — conv_xl16 otherwise
-            // (measured, bf16: k = 3 / 7 / 11: 471 / 754 / 967 us per pair against 527 / 700 / 903 for the two launches: k = 3 only)
-            const bool pair128 = g_voc_pair128 && co == 128 && rk == 3 && (v->precision == 1 || v->precision == 2);
-            // 16-bit, C = 128 (round 3): the pair in ONE launch with a single in-place image (81 KB: two workgroups per CU, 2 x 4 tiles per wave)
-            const bool pairw = g_voc_pairw && co == 128 && (v->precision == 1 || v->precision == 2);
-            // fp16x3 (round 3): the pair X-resident with (hi, lo) images, C <= 128 (resblock_pair16x3.hip; same bits as the two conv16 launches)
-            const bool pair3 = g_voc_pair3 && v->precision == 3 && co <= 128;
-            bool pair_ok = g_voc_pair && (co <= 64 || pair128 || pairw || pair3) && (v->precision != 3 || pair3) &&
-                                 (v->precision ? (pair16_pays && v->c1f[r][0][v->precision - 1] != nullptr) : v->c1f32[r][0] != nullptr);
-            // fp32, C = 64, k >= 7, chip-filling launches (round 4): the pair as two Winograd launches (conv_xlw_kernel<64>: one wave per workgroup with both
-            // m-tiles, eight workgroups per CU) instead of the fused pair kernel — 10 / 15 products per output pair instead of 14 / 22 outweigh xt's trip through HBM (k = 11: 2 x 1225 against 3217 us; k = 7: -0.3 ms per batch)
-            // the launch-size gate of the fp32 Winograd forms (here, qpair below, conv_xlq / conv_xlw through wino_force); vocoder option "batch_invariant":
-            // the large-launch branch at every size, so that a row's bits do not depend on the batch (every other size-dependent choice of this function —
-            // conv_xl's m-tile split "voc_xl_split", the generic conv's tile configurations, the upsamplers' phase split — only divides the same work)
-            const bool big_launch = v->batch_invariant || (long)((To + 63) / 64) * B >= 1024;
-            const bool xw64 = g_voc_wino64 && g_voc_wino && v->winograd && !v->precision && co == 64 && rk >= g_voc_wino64_k && v->c1w32[r][0] && v->c2w32[r][0] &&
-                              (g_voc_wino == 2 || big_launch);
-            if (xw64) pair_ok = false;
-            // round 6: k = 3 pairs at C = 64 / 128 with both convs in the F(4,3) form and xt kept on the CU (conv_xlq_pair.hip): at C = 128 the two conv_xlq
-            // launches below without xt's trip through HBM and the residual's second read (five tensor passes -> two; the same products on quads one frame apart: fp32
-            // Winograd rounding between the two); at C = 64 half the MFMAs of the direct pair kernel.  64.4 -> 62.9 ms per 32 x 512-frame batch
-            bool qpair = g_voc_qpair && g_voc_wino && g_voc_wino43 && v->winograd && !v->precision && rk == 3 && (co == 64 || co == 128) &&
-                         (g_voc_qpair == 2 || g_voc_wino == 2 || big_launch);
-            for (int mi = 0; mi < 3 && qpair; ++mi) qpair = v->c1q32[r][mi] && v->c2q32[r][mi];
-            for (int mi = 0; mi < 3 && qpair; ++mi) {
-                const bool lastm = mi == 2;
-                if (ss && lastm && j > 0) HIPCHK(hipStreamWaitEvent(q, j == 1 ? ss->done0 : ss->done1, 0));
-                PairArgs pa;
-                memset(&pa, 0, sizeof(pa));
-                pa.x = xr; pa.y = lastm ? bufS : (mi == 0 ? bR : bT);
-                pa.b1 = v->c1[r][mi].bias; pa.b2 = v->c2[r][mi].bias;
-                pa.w1f = v->c1q32[r][mi]; pa.w2f = v->c2q32[r][mi];
-                pa.bstride = cs; pa.B = B; pa.C = co; pa.T = To; pa.ld = ld; pa.k = rk; pa.dil = v->rb_dil[mi];
-                pa.accum = lastm && j > 0; pa.slope = 0.1f;
-                if (cmtts_launch_conv_xlq_pair(&pa, (void*)q) != 0) return fail(CMTTS_E_HIP, "conv_xlq_pair launch failed");
-                if (ss && lastm && j < 2) HIPCHK(hipEventRecord(j == 0 ? ss->done0 : ss->done1, q));
-                xr = pa.y;
-            }
-            if (qpair) continue;
-            for (int mi = 0; mi < 3 && pair_ok; ++mi) {
-                const bool lastm = mi == 2;
-                if (ss && lastm && j > 0) HIPCHK(hipStreamWaitEvent(q, j == 1 ? ss->done0 : ss->done1, 0));
-                PairArgs pa;
-                memset(&pa, 0, sizeof(pa));
-                pa.x = xr; pa.y = lastm ? bufS : (mi == 0 ? bR : bT);
-                pa.b1 = v->c1[r][mi].bias; pa.b2 = v->c2[r][mi].bias;
-                if (v->precision) { pa.w1f = v->c1f[r][mi][v->precision - 1]; pa.w2f = v->c2f[r][mi][v->precision - 1]; }
-                else { pa.w1f = v->c1f32[r][mi]; pa.w2f = v->c2f32[r][mi]; }
-                pa.bstride = cs; pa.B = B; pa.C = co; pa.T = To; pa.ld = ld; pa.k = rk; pa.dil = v->rb_dil[mi];
-                pa.accum = lastm && j > 0; pa.slope = 0.1f;
-                int prc;
-                if (!v->precision) prc = cmtts_launch_resblock_pair(&pa, (void*)q);
-                else if (pair3) prc = cmtts_launch_resblock_pair16x3(&pa, (void*)q);
-                else if (pairw) prc = cmtts_launch_resblock_pairw16(&pa, v->precision, (void*)q);
-                else prc = cmtts_launch_resblock_pair16(&pa, v->precision, (void*)q);
-                if (prc == -2 && mi == 0) {      // this (C, k, dilation) is not covered by the pair kernels: the per-conv path below
-                    pair_ok = false;            // (nothing has been launched for this ResBlock yet)
-                    break;
-                }
-                if (prc != 0) return fail(CMTTS_E_HIP, "resblock_pair launch failed");
-                if (ss && lastm && j < 2) HIPCHK(hipEventRecord(j == 0 ? ss->done0 : ss->done1, q));
-                xr = pa.y;
-            }
-            for (int mi = 0; mi < 3 && !pair_ok; ++mi) {   // ResBlock.forward (:96-103)
-                const int dil = v->rb_dil[mi];
-                const bool lastm = mi == 2;
-                if (g_voc_xl && !v->precision && (co >= 128 || xw64) && v->c1f32[r][mi]) {   // wide stages: X-resident single convs
-                    ConvXlArgs xa;
-                    memset(&xa, 0, sizeof(xa));
-                    // round 4: the Winograd form of both convs (conv_xlw_kernel: 4 / 10 / 15 products per output pair instead of 6 / 14 / 22)
-                    const bool xw = g_voc_wino && v->winograd && v->c1w32[r][mi] && v->c2w32[r][mi];
-                    xa.x = xr; xa.y = bT; xa.wf = xw ? v->c1w32[r][mi] : v->c1f32[r][mi]; xa.bias = v->c1[r][mi].bias;
-                    xa.bstride = cs; xa.B = B; xa.C = co; xa.T = To; xa.ld = ld; xa.k = rk; xa.dil = dil; xa.slope = 0.1f; xa.wino_force = g_voc_wino == 2 || v->batch_invariant;
-                    // round 5: dilation-1 convs (every conv2, conv1 of the first pair) in the F(4,3) form (conv_xlq_kernel: 6 / 16 / 24 products per quad of outputs where
-                    // the F(2,3) tap groups take 8 / 20 / 30); -2 = launch too small or shape not covered: the F(2,3) form, then the direct one
-                    int rc1 = -2;
-                    // (dilation 3 in that form everywhere, dilation 5 only at C = 256 or k = 3: the five-class tiles of C = 128 / 64 (one workgroup fewer per CU, 15 of
-                    //  16 quad lanes, strided stores) are slower than the F(2,3) pair tiles at k = 7 / 11 — 3.63 vs 2.44 ms at C = 128, k = 11; voc_wino43 = 3 forces them for tests)
-                    if (xw && g_voc_wino43 && (dil == 1 || (g_voc_wino43 == 1 && (co == 256 || dil == 3 || rk == 3)) || g_voc_wino43 == 3) && v->c1q32[r][mi]) { xa.wf = v->c1q32[r][mi]; rc1 = cmtts_launch_conv_xlq(&xa, (void*)q); if (rc1 == -2) xa.wf = v->c1w32[r][mi]; }
-                    if (rc1 == -2 && xw) rc1 = cmtts_launch_conv_xlw(&xa, (void*)q);
-                    const bool xw1 = rc1 == 0;
-                    if (rc1 == -2) { xa.wf = v->c1f32[r][mi]; rc1 = cmtts_launch_conv_xl(&xa, (void*)q); }
-                    if (rc1 == -3) return fail(CMTTS_E_HIP, "conv_xl launch failed");
-                    if (rc1 == 0) {
-                        if (ss && lastm && j > 0) HIPCHK(hipStreamWaitEvent(q, j == 1 ? ss->done0 : ss->done1, 0));
-                        // the residual operand is read at the positions this launch writes when y == res (in place: safe,
-                        // every output element reads only its own residual); the INPUT must not alias the output
-                        xa.x = bT; xa.y = lastm ? bufS : bR; xa.wf = xw1 ? v->c2w32[r][mi] : v->c2f32[r][mi]; xa.bias = v->c2[r][mi].bias;
-                        xa.res = xr; xa.dil = 1; xa.accum = lastm && j > 0;
-                        int rc2 = -2;
-                        if (xw1 && g_voc_wino43 && v->c2q32[r][mi]) { xa.wf = v->c2q32[r][mi]; rc2 = cmtts_launch_conv_xlq(&xa, (void*)q); if (rc2 == -2) xa.wf = v->c2w32[r][mi]; }
-                        if (rc2 == -2) rc2 = xw1 ? cmtts_launch_conv_xlw(&xa, (void*)q) : cmtts_launch_conv_xl(&xa, (void*)q);
-                        if (rc2 != 0) return fail(CMTTS_E_HIP, "conv_xl launch failed");
-                        if (ss && lastm && j < 2) HIPCHK(hipEventRecord(j == 0 ? ss->done0 : ss->done1, q));
-                        xr = bR;
-                        continue;
-                    }
-                }
-                if (g_voc_xl16 && (v->precision == 1 || v->precision == 2) && co >= 128 && v->c1f[r][mi][v->precision - 1]) {
-                    // wide stages, 16-bit operands: X-resident single convs (conv_xl16_kernel); xt crosses HBM in 16 bits
-                    ConvXlArgs xa;
-                    memset(&xa, 0, sizeof(xa));
-                    xa.x = xr; xa.y = bT; xa.wf = (const float*)v->c1f[r][mi][v->precision - 1]; xa.bias = v->c1[r][mi].bias;
-                    xa.bstride = cs; xa.B = B; xa.C = co; xa.T = To; xa.ld = ld; xa.k = rk; xa.dil = dil; xa.slope = 0.1f;
-                    const int rc1 = cmtts_launch_conv_xl16(&xa, v->precision, 1, (void*)q);
-                    if (rc1 == -3) return fail(CMTTS_E_HIP, "conv_xl16 launch failed");
-                    if (rc1 == 0) {
-                        if (ss && lastm && j > 0) HIPCHK(hipStreamWaitEvent(q, j == 1 ? ss->done0 : ss->done1, 0));
-                        xa.x = bT; xa.y = lastm ? bufS : bR; xa.wf = (const float*)v->c2f[r][mi][v->precision - 1];
-                        xa.bias = v->c2[r][mi].bias; xa.res = xr; xa.dil = 1; xa.accum = lastm && j > 0;
-                        if (cmtts_launch_conv_xl16(&xa, v->precision, 2, (void*)q) != 0) return fail(CMTTS_E_HIP, "conv_xl16 launch failed");
-                        if (ss && lastm && j < 2) HIPCHK(hipEventRecord(j == 0 ? ss->done0 : ss->done1, q));
-                        xr = bR;
-                        continue;
-                    }
-                }
-                if (g_voc_pair3 && v->precision == 3 && co == 256 && v->c1f[r][mi][2]) {
-                    // fp16x3, C = 256: X-resident single convs with (hi, lo) images (conv_xl16x3_kernel); xt crosses HBM in fp32
-                    ConvXlArgs xa;
-                    memset(&xa, 0, sizeof(xa));
-                    xa.x = xr; xa.y = bT; xa.wf = (const float*)v->c1f[r][mi][2]; xa.bias = v->c1[r][mi].bias;
-                    xa.bstride = cs; xa.B = B; xa.C = co; xa.T = To; xa.ld = ld; xa.k = rk; xa.dil = dil; xa.slope = 0.1f;
-                    const int rc1 = cmtts_launch_conv_xl16x3(&xa, (void*)q);
-                    if (rc1 == -3) return fail(CMTTS_E_HIP, "conv_xl16x3 launch failed");
-                    if (rc1 == 0) {
-                        if (ss && lastm && j > 0) HIPCHK(hipStreamWaitEvent(q, j == 1 ? ss->done0 : ss->done1, 0));
-                        xa.x = bT; xa.y = lastm ? bufS : bR; xa.wf = (const float*)v->c2f[r][mi][2];
-                        xa.bias = v->c2[r][mi].bias; xa.res = xr; xa.dil = 1; xa.accum = lastm && j > 0;
-                        if (cmtts_launch_conv_xl16x3(&xa, (void*)q) != 0) return fail(CMTTS_E_HIP, "conv_xl16x3 launch failed");
-                        if (ss && lastm && j < 2) HIPCHK(hipEventRecord(j == 0 ? ss->done0 : ss->done1, q));
-                        xr = bR;
-                        continue;
-                    }
-                }
-                ConvArgs a = conv_args(v->c1[r][mi], xr, To, ld, cs, bT, ld, cs, To);
-                a.dil = dil; a.pad = (rk * dil - dil) / 2; a.pre_slope = 0.1f;
-                if (v->precision == 3) {                  // fp16x3: fp32 xt in HBM, operands split into hi + lo fp16 while staged
-                    if (cmtts_launch_conv16(&a, v->c1f[r][mi][2], 3, B, (void*)q) != 0)
-                        return fail(CMTTS_E_HIP, "conv16 launch failed");
-                } else if (v->precision) {
-                    a.y16 = 1; a.y16_slope = 0.1f;        // xt crosses HBM as convert(leaky_relu(xt)) in 16 bits
-                    if (cmtts_launch_conv16(&a, v->c1f[r][mi][v->precision - 1], v->precision, B, (void*)q) != 0)
-                        return fail(CMTTS_E_HIP, "conv16 launch failed");
-                } else {
-                    CHK(launch(a, EPI_PLAIN, B, q));
-                }
-                // the MRF sum accumulates in ResBlock order (bit-identical to the in-line order): the last conv of
-                // chain j waits for the last conv of chain j-1
-                if (ss && lastm && j > 0) HIPCHK(hipStreamWaitEvent(q, j == 1 ? ss->done0 : ss->done1, 0));
-                ConvArgs b = conv_args(v->c2[r][mi], bT, To, ld, cs, lastm ? bufS : bR, ld, cs, To);
-                b.pre_slope = 0.1f;
-                b.out[0].res = xr; b.out[0].r_zs0 = cs; b.out[0].ldr = ld;
-                b.out[0].accum = lastm && j > 0;
-                if (v->precision == 3) {
-                    if (cmtts_launch_conv16(&b, v->c2f[r][mi][2], 3, B, (void*)q) != 0)
-                        return fail(CMTTS_E_HIP, "conv16 launch failed");
-                } else if (v->precision) {
-                    b.x16 = 1;
-                    if (cmtts_launch_conv16(&b, v->c2f[r][mi][v->precision - 1], v->precision, B, (void*)q) != 0)
-                        return fail(CMTTS_E_HIP, "conv16 launch failed");
-                } else {
-                    CHK(launch(b, EPI_PLAIN, B, q));
-                }
-                if (ss && lastm && j < 2) HIPCHK(hipEventRecord(j == 0 ? ss->done0 : ss->done1, q));
-                xr = bR;
-            }
-        }
-        if (ss) {   // the next stage (and conv_post) read the sum: chain 2's last conv is the last writer; chain 1 is
-                    // ordered before it, but its stream must also be idle before its buffers are reused
-            HIPCHK(hipEventRecord(ss->join, ss->side));
-            HIPCHK(hipEventRecord(ss->join2, ss->side2));
-            HIPCHK(hipStreamWaitEvent(s, ss->join, 0));
-            HIPCHK(hipStreamWaitEvent(s, ss->join2, 0));
-        }
-        float* t = bufA; bufA = bufS; bufS = t;
-        Ti = To; ch = co;
-    }
-    *x_out = bufA; *ch_out = ch; *Ti_out = Ti; *ld_out = Ti + P;
-    return 0;
-}
-int cmtts_vocoder_forward(cmtts_vocoder* v, const float* mel_ct, int B, int T, float* wav, void* ws, size_t ws_bytes,
-                          void* stream) {
-    if (!v || !v->finalized) return fail(CMTTS_E_INVALID, "vocoder not finalized");
-    if (!mel_ct || !wav || !ws || B <= 0 || T <= 0) return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward: bad argument");
-    if (ws_bytes < cmtts_vocoder_workspace_bytes(v, B, T)) return fail(CMTTS_E_WORKSPACE, "vocoder workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    const float* x = nullptr;
-    int ch = 0, Ti = 0, ld = 0;
-    if (const int rc = vocoder_generator(v, mel_ct, B, T, ws, s, &x, &ch, &Ti, &ld)) return rc;
-    // x = leaky_relu(xs / 3) [slope 0.01] -> conv_post -> tanh (:161-163)
-    k_conv_post(x, v->post_w, v->post_b, 3.0f, 0.01f, wav, B, ch, Ti, ld, v->post_k, s);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ---- streaming: a batch of mel windows through the generator, int16 chunks of the window cores out (stream_windows.hip)
-int cmtts_vocoder_halo_frames(const cmtts_vocoder* v) {
-    // output frame f depends on mel frames [f - H, f + H]: the samples of frame f propagated backwards through conv_post,
-    // every MRF (widest ResBlock: a (conv1 dilation d, conv2) pair widens by (d + 1)(k - 1) / 2), every ConvTranspose1d and
-    // conv_pre (config.HifiGanConfig.halo_frames walks the same chain)
-    if (!v) return fail(CMTTS_E_INVALID, "cmtts_vocoder_halo_frames: null argument");
-    long hop = 1;
-    for (int i = 0; i < 4; ++i) hop *= v->up_rate[i];
-    const long f = 1L << 20;
-    long lo = f * hop - v->post_k / 2, hi = (f + 1) * hop - 1 + v->post_k / 2;
-    int w = 0;
-    for (int j = 0; j < 3; ++j) w = std::max(w, (v->rb_dil[0] + v->rb_dil[1] + v->rb_dil[2] + 3) * (v->rb_kernel[j] - 1) / 2);
-    for (int i = 3; i >= 0; --i) {
-        const long u = v->up_rate[i], k = v->up_kernel[i], p = (k - u) / 2;
-        lo -= w; hi += w;
-        const long a = lo + p - (k - 1), b = hi + p;          // y[t] = sum over i u + j - p = t (j in [0, k)) of x[i] w[j]
-        lo = a >= 0 ? (a + u - 1) / u : -((-a) / u);
-        hi = b >= 0 ? b / u : -((-b + u - 1) / u);
-    }
-    lo -= 3; hi += 3;                                          // conv_pre k = 7
-    return (int)std::max(f - lo, hi - f);
-}
-size_t cmtts_vocoder_windows_workspace_bytes(const cmtts_vocoder* v, int N, int Tw) {
-    if (N <= 0 || Tw <= 0) return 0;
-    // the gathered windows [N][80][Tw] and the validated table [N][4], then the generator's workspace for (N, Tw)
-    return (((size_t)N * 80 * Tw * sizeof(float) + 255) & ~(size_t)255) + (((size_t)N * sizeof(StreamWindow) + 255) & ~(size_t)255) +
-           cmtts_vocoder_workspace_bytes(v, N, Tw);
-}
-int cmtts_vocoder_forward_windows(cmtts_vocoder* v, const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, int core,
-                                  int16_t* pcm, float max_wav_value, void* ws, size_t ws_bytes, void* stream) {
-    if (!v || !v->finalized) return fail(CMTTS_E_INVALID, "vocoder not finalized");
-    if (!mel_ct || !windows || !pcm || !ws) return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward_windows: null argument");
-    if (B <= 0 || T <= 0 || N <= 0 || Tw <= 0 || core <= 0)
-        return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward_windows: B, T, N, Tw and core must be positive");
-    if (Tw > T) return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward_windows: Tw > T");
-    if (!(max_wav_value > 0.f && max_wav_value <= 32768.f)) return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward_windows: max_wav_value outside (0, 32768]");
-    if (ws_bytes < cmtts_vocoder_windows_workspace_bytes(v, N, Tw)) return fail(CMTTS_E_WORKSPACE, "cmtts_vocoder_forward_windows: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    // The table is validated on the host before anything launches: a page-locked host table is read in place and copied into the
-    // workspace on `stream` (no synchronisation; the caller keeps it unchanged until the call's work has completed); a device table is
-    // read back first, which synchronises `stream`.
-    std::vector<StreamWindow> tab(N);
-    hipPointerAttribute_t at{};
-    const bool known = hipPointerGetAttributes(&at, windows) == hipSuccess;
-    if (!known) (void)hipGetLastError();
-    const bool on_host = known && at.type == hipMemoryTypeHost;
-    const bool on_dev = known && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeUnified);
-    if (!on_host && !on_dev) return fail(CMTTS_E_INVALID, "cmtts_vocoder_forward_windows: the window table must be device or page-locked host memory");
-    if (on_host) {
-        memcpy(tab.data(), windows, (size_t)N * sizeof(StreamWindow));
-    } else {
-        HIPCHK(hipMemcpyAsync(tab.data(), windows, (size_t)N * sizeof(StreamWindow), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    for (int n = 0; n < N; ++n) {
-        const StreamWindow& w = tab[n];
-        char msg[200];
-        const char* bad = w.b < 0 || w.b >= B                                   ? "utterance outside [0, B)"
-                          : w.start < 0 || (long)w.start + Tw > T              ? "window outside [0, T)"
-                          : w.core_len <= 0 || w.core_len > core               ? "core_len outside [1, core]"
-                          : w.core_off < 0 || (long)w.core_off + w.core_len > Tw ? "core_off + core_len > Tw"
-                                                                                  : nullptr;
-        if (bad) {
-            snprintf(msg, sizeof msg, "cmtts_vocoder_forward_windows: window %d (%d, %d, %d, %d): %s", n, w.b, w.start, w.core_off, w.core_len, bad);
-            return fail(CMTTS_E_INVALID, msg);
-        }
-    }
-    Carver cv(ws);
-    float* mel_w = cv.take<float>((size_t)N * 80 * Tw);
-    StreamWindow* win = cv.take<StreamWindow>(N);
-    void* gws = cv.base + ((cv.off + 255) & ~(size_t)255);
-    if (on_host) HIPCHK(hipMemcpyAsync(win, windows, (size_t)N * sizeof(StreamWindow), hipMemcpyHostToDevice, s));
-    else HIPCHK(hipMemcpyAsync(win, windows, (size_t)N * sizeof(StreamWindow), hipMemcpyDeviceToDevice, s));
-    if (cmtts_launch_mel_window_gather(mel_ct, 80, T, win, N, Tw, mel_w, (void*)s) != 0) return fail(CMTTS_E_HIP, "mel window gather launch failed");
-    const float* x = nullptr;
-    int ch = 0, Ti = 0, ld = 0;
-    if (const int rc = vocoder_generator(v, mel_w, N, Tw, gws, s, &x, &ch, &Ti, &ld)) return rc;
-    long hop = 1;
-    for (int i = 0; i < 4; ++i) hop *= v->up_rate[i];
-    // x = leaky_relu(xs / 3) [slope 0.01] -> conv_post -> tanh -> int16, core columns only
-    const int rc = cmtts_launch_conv_post_windows(x, v->post_w, v->post_b, 3.0f, 0.01f, win, N, ch, Ti, ld, v->post_k, (int)hop, core,
-                                                  max_wav_value, pcm, (void*)s);
-    if (rc == -2) return fail(CMTTS_E_UNSUPPORTED, "cmtts_vocoder_forward_windows: conv_post kernel wider than 7");
-    if (rc != 0) return fail(CMTTS_E_HIP, "conv_post windows launch failed");
-    return 0;
-}
-// Host copy of an int32 table that is device or page-locked host memory (the contract of cmtts_vocoder_forward_windows): a host
-// table is read in place, a device table is read back on `s`, which synchronises it.  *on_host tells which it was.
-static int fetch_table(const char* who, const void* table, void* host_copy, size_t bytes, hipStream_t s, bool* on_host) {
-    hipPointerAttribute_t at{};
-    const bool known = hipPointerGetAttributes(&at, table) == hipSuccess;
-    if (!known) (void)hipGetLastError();
-    *on_host = known && at.type == hipMemoryTypeHost;
-    const bool on_dev = known && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeUnified);
-    if (!*on_host && !on_dev) return fail(CMTTS_E_INVALID, std::string(who) + ": the table must be device or page-locked host memory");
-    if (*on_host) {
-        memcpy(host_copy, table, bytes);
-    } else {
-        HIPCHK(hipMemcpyAsync(host_copy, table, bytes, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return 0;
-}
-int cmtts_vocoder_forward_windows_f32(cmtts_vocoder* v, const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, int core,
-                                      int margin_frames, float* wav_rows, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "cmtts_vocoder_forward_windows_f32";
-    if (!v || !v->finalized) return fail(CMTTS_E_INVALID, "vocoder not finalized");
-    if (!mel_ct || !windows || !wav_rows || !ws) return fail(CMTTS_E_INVALID, std::string(who) + ": null argument");
-    if (B <= 0 || T <= 0 || N <= 0 || Tw <= 0 || core <= 0) return fail(CMTTS_E_INVALID, std::string(who) + ": B, T, N, Tw and core must be positive");
-    if (Tw > T) return fail(CMTTS_E_INVALID, std::string(who) + ": Tw > T");
-    if (margin_frames < 0 || (Tw != T && (long)core + 2L * margin_frames > Tw))
-        return fail(CMTTS_E_INVALID, std::string(who) + ": margin_frames outside [0, (Tw - core) / 2] of a window narrower than T");
-    if (ws_bytes < cmtts_vocoder_windows_workspace_bytes(v, N, Tw)) return fail(CMTTS_E_WORKSPACE, std::string(who) + ": workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<StreamWindow> tab(N);
-    bool on_host = false;
-    CHK(fetch_table(who, windows, tab.data(), (size_t)N * sizeof(StreamWindow), s, &on_host));
-    for (int n = 0; n < N; ++n) {
-        const StreamWindow& w = tab[n];
-        char msg[200];
-        const char* bad = w.b < 0 || w.b >= B                                   ? "utterance outside [0, B)"
-                          : w.start < 0 || (long)w.start + Tw > T              ? "window outside [0, T)"
-                          : w.core_len <= 0 || w.core_len > core               ? "core_len outside [1, core]"
-                          : w.core_off < 0 || (long)w.core_off + w.core_len > Tw ? "core_off + core_len > Tw"
-                                                                                  : nullptr;
-        if (bad) {
-            snprintf(msg, sizeof msg, "%s: window %d (%d, %d, %d, %d): %s", who, n, w.b, w.start, w.core_off, w.core_len, bad);
-            return fail(CMTTS_E_INVALID, msg);
-        }
-    }
-    Carver cv(ws);
-    float* mel_w = cv.take<float>((size_t)N * 80 * Tw);
-    StreamWindow* win = cv.take<StreamWindow>(N);
-    void* gws = cv.base + ((cv.off + 255) & ~(size_t)255);
-    HIPCHK(hipMemcpyAsync(win, windows, (size_t)N * sizeof(StreamWindow), on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-    if (cmtts_launch_mel_window_gather(mel_ct, 80, T, win, N, Tw, mel_w, (void*)s) != 0) return fail(CMTTS_E_HIP, "mel window gather launch failed");
-    const float* x = nullptr;
-    int ch = 0, Ti = 0, ld = 0;
-    if (const int rc = vocoder_generator(v, mel_w, N, Tw, gws, s, &x, &ch, &Ti, &ld)) return rc;
-    long hop = 1;
-    for (int i = 0; i < 4; ++i) hop *= v->up_rate[i];
-    // x = leaky_relu(xs / 3) [slope 0.01] -> conv_post -> tanh, core and margin columns only, fp32
-    const int rc = cmtts_launch_conv_post_windows_f32(x, v->post_w, v->post_b, 3.0f, 0.01f, win, N, ch, Ti, ld, v->post_k, (int)hop, core,
-                                                      margin_frames, wav_rows, (void*)s);
-    if (rc == -2) return fail(CMTTS_E_UNSUPPORTED, std::string(who) + ": conv_post kernel wider than 7");
-    if (rc != 0) return fail(CMTTS_E_HIP, "conv_post windows launch failed");
-    return 0;
-}
-
 // ---- output sample rates and encodings (resample.hip)
 struct cmtts_resampler {
     int L = 0, M = 0, half = 0, R = 0;
@@ -2426,13 +1927,6 @@ int cmtts_loudness_measure(const float* wav, int rows, int64_t ld, const int32_t
     if (rc != 0) return fail(CMTTS_E_HIP, "loudness finish launch failed");
     return 0;
 }
-int cmtts_internal_mel_window_gather(const float* mel_ct, int B, int T, const int32_t* windows, int N, int Tw, float* out, void* stream) {
-    (void)B;
-    if (!mel_ct || !windows || !out || N <= 0 || Tw <= 0 || Tw > T) return fail(CMTTS_E_INVALID, "cmtts_internal_mel_window_gather: bad argument");
-    return cmtts_launch_mel_window_gather(mel_ct, 80, T, (const StreamWindow*)windows, N, Tw, out, stream) == 0 ? 0
-                                                                                                              : fail(CMTTS_E_HIP, "gather launch failed");
-}
-
 int cmtts_internal_duration_fit(float* d_rounded, int* cum, int64_t* mel_len, const int64_t* src_lens, const int32_t* seg, const int32_t* target,
                                 int32_t* unmet, int B, int L, int n_seg, void* stream) {
     if (!d_rounded || !cum || !mel_len || !src_lens || !target || B <= 0 || L <= 0 || n_seg < 1 || (!seg && n_seg != 1) ||
@@ -2449,19 +1943,6 @@ int cmtts_internal_duration_fit(float* d_rounded, int* cum, int64_t* mel_len, co
 //   cmtts_vocoder_set_option    properties of a model, not of the process
 //   cmtts_internal_set          A/B switches between a fused kernel and the path it replaces (bitwise equal, used by tests/ and
 //                               tools/ for cross-checks and measurements); declared in csrc/internal_hooks.h, NOT part of the ABI
-struct Knob { const char* name; int* var; int lo, hi; };
-static int knob_set(const Knob* tab, size_t n, const char* name, int value, bool* found) {
-    for (size_t i = 0; i < n; ++i)
-        if (!strcmp(name, tab[i].name)) {
-            *found = true;
-            const int prev = *tab[i].var;
-            if (value >= tab[i].lo && value <= tab[i].hi) *tab[i].var = value;
-            return prev;
-        }
-    *found = false;
-    return 0;
-}
-
 int cmtts_set_option(const char* name, int value) {
     if (!name) return fail(CMTTS_E_INVALID, "cmtts_set_option: null name");
     if (!strcmp(name, "cooperative_launch")) {   // persistent denoiser through hipLaunchCooperativeKernel: 0 never, 1 always, 2 = automatic
@@ -2498,19 +1979,6 @@ int cmtts_model_set_option(cmtts_model* m, const char* name, int value) {
     return fail(CMTTS_E_INVALID, "cmtts_model_set_option: unknown option");
 }
 
-int cmtts_vocoder_set_option(cmtts_vocoder* v, const char* name, int value) {
-    if (!v || !name) return fail(CMTTS_E_INVALID, "cmtts_vocoder_set_option: null argument");
-    const Knob tab[] = {
-        {"ups16", &v->ups16, 0, 1},                      // 16-bit modes: 16-bit operands in the upsamplers too (1) or fp32 upsamplers (0)
-        {"winograd", &v->winograd, 0, 1},                // fp32 generator: the ResBlock convs of the C >= 128 stages in their Winograd form (default 1; 0 = the direct form)
-        {"batch_invariant", &v->batch_invariant, 0, 1},  // fp32 generator: the large-launch forms at every launch size (default 0)
-    };
-    bool found;
-    const int prev = knob_set(tab, sizeof(tab) / sizeof(tab[0]), name, value, &found);
-    if (found) return prev;
-    return fail(CMTTS_E_INVALID, "cmtts_vocoder_set_option: unknown option");
-}
-
 // csrc/internal_hooks.h — fused kernel vs the path it replaces; every pair is bitwise equal (tests/test_gpu_parity.py)
 int cmtts_internal_set(const char* name, int value) {
     if (!name) return fail(CMTTS_E_INVALID, "cmtts_internal_set: null name");
@@ -2533,30 +2001,17 @@ int cmtts_internal_set(const char* name, int value) {
         {"attn_fused", &g_attn_fused, 0, 1},       // fused attention kernel vs three launches
         {"pred_xl", &g_pred_xl, 0, 1},             // frame-level predictor convs on conv_xl
         {"pred_head", &g_pred_head, 0, 1},         // LayerNorm + linear head in one launch
-        {"voc_pair", &g_voc_pair, 0, 2},           // HiFi-GAN ResBlock pairs (C <= 64) as one launch
-        {"voc_pair3", &g_voc_pair3, 0, 1},         // fp16x3 pairs: one X-resident launch (resblock_pair16x3.hip)
-        {"voc_pairw", &g_voc_pairw, 0, 1},         // 16-bit C = 128 pairs: one launch, one in-place LDS image (resblock_pairw16.hip)
-        {"voc_pair128", &g_voc_pair128, 0, 1},     // 16-bit C = 128, k = 3 pair kernel (two images, one workgroup per CU; only when voc_pairw = 0)
-        {"voc_rb16", &g_voc_rb16, 0, 2},           // 16-bit whole-ResBlock kernel: 0 never, 1 where it pays, 2 always
-        {"voc_xl", &g_voc_xl, 0, 1},               // fp32 wide-stage convs on conv_xl
-        {"voc_wino64_k", &g_voc_wino64_k, 3, 99},
-        {"voc_wino43", &g_voc_wino43, 0, 3},       // fp32 dilation-1 convs of the Winograd path as F(4,3) (conv_xlq_kernel; NOT bitwise F(2,3) or direct)
-        {"voc_qpair", &g_voc_qpair, 0, 2},         // fp32 k = 3 pairs at C = 64 / 128 of the Winograd path as ONE F(4,3) launch (conv_xlq_pair.hip; NOT bitwise the forms it replaces)
-        {"voc_wino64", &g_voc_wino64, 0, 1},       // fp32 C = 64 stage, k >= voc_wino64_k: two conv_xlw launches per pair (with voc_wino) instead of the pair kernel
-        {"voc_wino", &g_voc_wino, 0, 2},           // fp32 wide-stage convs in their Winograd form (NOT bitwise: the A/B twin of the vocoder option "winograd")
-        {"voc_xl16", &g_voc_xl16, 0, 1},           // 16-bit wide-stage convs on conv_xl16
-        {"voc_upsT", &g_voc_upsT, 0, 1},           // upsamplers on convT_xl
-        {"post_v4", &g_post_v4, 0, 1},             // conv_post with 16-byte loads
         {"pred_wino", &g_pred_wino, 0, 1},         // pitch predictor's k = 5 convs as F(4,3) tap groups (NOT bitwise the direct form)
         {"energy_head", &g_energy_head, 0, 1},     // energy bucketize + embedding add inside the energy predictor's head launch (same bits)
         {"stats_mlp", &g_stats_mlp, 0, 1},         // cwt_stats_layers as one launch (same bits)
         {"text_xt16", &g_conv_xt16, 0, 1},         // text16 convs with K = 256 on the X-resident 16-bit kernel (conv_xt16.hip) instead of the chunked one
     };
-    if (!strcmp(name, "voc_xl_split")) return cmtts_xl_set_split(value);
     if (!strcmp(name, "attn_qb")) return cmtts_attention_set_qb(value);       // attention.hip: queries split over workgroups (round 6; same bits)
     if (!strcmp(name, "xres_nt")) return cmtts_xres_set_nt(value);            // conv_xres tile width for launches that do not choose one (measurements)      // conv_xl: m-tiles over several workgroups for launches of a few column tiles
     bool found;
-    const int prev = knob_set(tab, sizeof(tab) / sizeof(tab[0]), name, value, &found);
+    int prev = vocoder_internal_set(name, value, &found);      // vocoder.hip: voc_*, post_v4
+    if (found) return prev;
+    prev = knob_set(tab, sizeof(tab) / sizeof(tab[0]), name, value, &found);
     if (found) return prev;
     return fail(CMTTS_E_INVALID, "cmtts_internal_set: unknown switch");
 }
@@ -2642,12 +2097,6 @@ int cmtts_phoneme_marks(const float* d_rounded, const int64_t* src_lens, int B, 
         return fail(CMTTS_E_INVALID, "cmtts_phoneme_marks: bad argument");
     k_phoneme_marks(d_rounded, src_lens, marks, B, L, T, hop, up, down, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int cmtts_vocoder_set_precision(cmtts_vocoder* v, int mode) {
-    if (!v || mode < 0 || mode > 3) return fail(CMTTS_E_INVALID, "cmtts_vocoder_set_precision: mode 0 (fp32), 1 (bf16), 2 (fp16) or 3 (fp16x3)");
-    v->precision = mode;
     return 0;
 }
 

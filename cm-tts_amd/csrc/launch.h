@@ -1,0 +1,46 @@
+// What the host-side launch sequences (cmtts_api.hip: text, frame and denoiser side; vocoder.hip: the HiFi-GAN generator) share:
+// the generic conv's argument fill and launch, workspace carving, the library-owned side streams and the switch tables.
+// Like fail() in model.h: declared here, defined once in cmtts_api.hip unless noted; small things are inline.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include "model.h"
+#include "conv_args.h"
+
+// A plain Conv1d over [B][cin][ldx] -> [B][cout][ldy]: "same" padding, dilation 1, no activation; callers adjust the fields that differ.
+ConvArgs conv_args(const PackedConv& w, const float* X, int Tin, int ldx, long x_bs, float* Y, int ldy, long y_bs, int N);
+int launch(const ConvArgs& a, int epi, int nbatch, hipStream_t s);      // the generic fp32 conv kernel (conv_mfma.hip); fail()s on error
+
+struct Carver {      // consecutive 256-byte aligned slices of a caller-provided workspace
+    char* base;
+    size_t off = 0;
+    explicit Carver(void* b) : base((char*)b) {}
+    template <class T>
+    T* take(size_t n) {
+        off = (off + 255) & ~(size_t)255;
+        T* p = (T*)(base + off);
+        off += n * sizeof(T);
+        return p;
+    }
+};
+
+// Library-owned side streams of a caller stream (public option "branch_streams"): independent branches of a call are forked
+// from and joined back into the caller's stream with events.
+struct SideStream {
+    hipStream_t user, side;
+    hipEvent_t fork, join;
+    hipStream_t side2 = nullptr;                      // second side stream + chain events: the three ResBlocks of an MRF stage (vocoder.hip)
+    hipEvent_t join2 = nullptr, done0 = nullptr, done1 = nullptr;
+};
+SideStream* side_for(hipStream_t s);      // null: branch_streams is off or no stream could be had — the caller runs in line
+bool side2_ready(SideStream* ss);         // creates side2 / join2 / done0 / done1 on first use
+
+// Host copy of an int32 table that is device or page-locked host memory: a host table is read in place, a device table is read
+// back on `s`, which synchronises it.  *on_host tells which it was.  (vocoder.hip)
+int fetch_table(const char* who, const void* table, void* host_copy, size_t bytes, hipStream_t s, bool* on_host);
+
+// Named integer switches: knob_set returns the previous value (a value outside [lo, hi] only queries); *found = the name is in the table.
+struct Knob { const char* name; int* var; int lo, hi; };
+int knob_set(const Knob* tab, size_t n, const char* name, int value, bool* found);
+int vocoder_internal_set(const char* name, int value, bool* found);      // vocoder.hip: the generator's switches, asked first by cmtts_internal_set

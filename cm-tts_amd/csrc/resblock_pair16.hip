@@ -1,4 +1,5 @@
-// HiFi-GAN ResBlock pair with 16-bit MFMA operands (bf16 / fp16, fp32 accumulate) for the narrow stages (C = 64, 32):
+// HiFi-GAN ResBlock pair with 16-bit MFMA operands (bf16 / fp16, fp32 accumulate) for the narrow stages (C = 64, 32; C = 128 is
+// resblock_pairw16.inc's, any other shape returns -2 to the dispatch in vocoder.hip):
 //   xt = conv1(leaky_relu(x));  y = conv2(leaky_relu(xt)) + x      (hifigan/models.py:96-103)
 // in ONE launch — the 16-bit twin of resblock_pair.hip.  At 16x the fp32 MFMA rate these convs are bound by bytes, not
 // by the matrix pipe: the two-launch path moves 5 tensor passes per pair (read x, write xt16, read xt16, read x, write y);
@@ -8,7 +9,7 @@
 //
 //   * LDS: x^T tile [256 + 2*r1][C] and xt^T tile [256 + k - 1][C], 16-bit, row stride C + 4 halves: a B fragment (lane l:
 //     8 consecutive channels of column l & 31) is two conflict-free ds_read_b64 and a dilated tap is a row offset;
-//   * every wave owns ONE 32-row m-tile x NT 32-column n-tiles (C = 64: 1 x 4, C = 32: 1 x 2); weights stream L2 -> VGPR in
+//   * four waves, each ONE 32-row m-tile x NT 32-column n-tiles (C = 64: 1 x 4, C = 32: 1 x 2); weights stream L2 -> VGPR in
 //     MFMA A-fragment order, one global_load_dwordx4 per k-group of 16 channels feeding NT MFMAs, 4-deep ring;
 //   * same conversions (v_cvt_pk_{bf16,f16}_f32 of leaky_relu(.)), same (32-channel chunk, tap, k-group) accumulation
 //     order and the same epilogue expressions as conv_mfma16.hip => BITWISE equal to the two-launch 16-bit path.
@@ -26,9 +27,9 @@ namespace {
 
 
 template <int C, int KT, int MODE>
-__global__ __launch_bounds__(C == 128 ? 512 : 256, 2) void resblock_pair16_kernel(const PairArgs a) {
+__global__ __launch_bounds__(256, 2) void resblock_pair16_kernel(const PairArgs a) {
     constexpr int RS = C + CL16_PAD;
-    constexpr int NWAVES = C == 128 ? 8 : 4;                // C = 128 (round 2): 8 waves, one 151-KB workgroup per CU
+    constexpr int NWAVES = 4;
     constexpr int NT = (C / 32) * (N1 / 32) / NWAVES;       // 32x32 tiles per wave: one m-tile x NT n-tiles
     constexpr int WPM = NWAVES / (C / 32);                  // waves per m-tile
     constexpr int R2 = (KT - 1) / 2;
@@ -155,17 +156,12 @@ int launch_pair16(const PairArgs& a, hipStream_t stream) {
         attr_set = true;
     }
     dim3 grid((a.T + TT - 1) / TT, a.B);
-    hipLaunchKernelGGL((resblock_pair16_kernel<C, KT, MODE>), grid, dim3(C == 128 ? 512 : 256), lds, stream, a);
+    hipLaunchKernelGGL((resblock_pair16_kernel<C, KT, MODE>), grid, dim3(256), lds, stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 template <int MODE>
 int dispatch16(const PairArgs& a, hipStream_t s) {
-    if (a.C == 128) {
-        if (a.k == 3) return launch_pair16<128, 3, MODE>(a, s);
-        if (a.k == 7) return launch_pair16<128, 7, MODE>(a, s);
-        if (a.k == 11) return launch_pair16<128, 11, MODE>(a, s);
-    }
     if (a.C == 64) {
         if (a.k == 3) return launch_pair16<64, 3, MODE>(a, s);
         if (a.k == 7) return launch_pair16<64, 7, MODE>(a, s);

@@ -2164,10 +2164,12 @@ def test_persistent_denoiser_lp_bitwise(variant, B, T, dtype):
     assert torch.equal(one2, ref)
 
 
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_vocoder_mrf_streams_bitwise(dtype):
+@pytest.mark.parametrize("dtype,voc_wino", [pytest.param("fp32", None, id="fp32"), pytest.param("bf16", None, id="bf16"),
+                                            pytest.param("fp32", 2, id="fp32-voc_wino2"), pytest.param("fp16x3", None, id="fp16x3")])
+def test_vocoder_mrf_streams_bitwise(dtype, voc_wino):
     """Small batches: the three ResBlocks of an MRF stage run on three streams, their sum still accumulates in ResBlock
-    order -> bit-identical to the in-line order, call after call."""
+    order -> bit-identical to the in-line order, call after call.  voc_wino None: the library's default; 2 puts the fused F(4,3)
+    pairs and the conv_xlq / conv_xlw chain on the three streams, fp16x3 the pair16x3 / conv_xl16x3 forms."""
     host = _host()
     lib = _lib.load()
     hcfg = HifiGanConfig()
@@ -2175,6 +2177,7 @@ def test_vocoder_mrf_streams_bitwise(dtype):
     voc.set_precision(dtype)
     mel = (torch.randn(2, 80, 61, generator=torch.Generator().manual_seed(2)) * 1.5 - 4).to(DEV)
     prev = lib.cmtts_set_option(b"branch_streams", 0)
+    prev_w = None if voc_wino is None else _lib.internal_set(b"voc_wino", voc_wino)
     try:
         ref = voc(mel).clone()
         lib.cmtts_set_option(b"branch_streams", 1)
@@ -2183,6 +2186,8 @@ def test_vocoder_mrf_streams_bitwise(dtype):
             torch.cuda.synchronize()
             assert torch.equal(got, ref)
     finally:
+        if prev_w is not None:
+            _lib.internal_set(b"voc_wino", prev_w)
         lib.cmtts_set_option(b"branch_streams", prev)
 
 
