@@ -4,6 +4,8 @@
 
 struct AttnArgs {
     const float* qkv;     // [B][3*H*dh][ld] channel-major: rows [0, H*dh) = Q, [H*dh, 2*H*dh) = K, [2*H*dh, 3*H*dh) = V
+                          // Contract: every column [0, L) of every row holds a FINITE value, padded keys [lens[b], L) included (the QKV launch writes them) — their
+                          // probability is 0, and 0 times a non-finite V is NaN by IEEE; columns [L, ld) are never used
     float* out;           // [B][H*dh][ld] channel-major
     const int64_t* lens;  // [B] valid keys per utterance (key padding mask)
     long bstride, obstride;
