@@ -14,10 +14,16 @@
 //     the flag, no fences).  Granule slots alternate by layer parity: a workgroup can be at most one layer ahead
 //     of a neighbour, because finishing layer l+1 needs the neighbour's layer-l columns.
 //
+//   * the layer boundary (epilogue, publish, barrier (1)) is where no wave has MFMAs queued, so nothing in it waits for memory that could have been
+//     asked for earlier: the layer's row vectors (bo, d, the next layer's dp — 512 bytes per wave) are fetched behind the projection's first ring groups
+//     and go through 512 bytes of per-wave LDS (Winograd instances), the halo entry's dp is loaded with its gathers ahead of the neighbour wait,
+//     the skip sum is formed in the epilogue, and the x' stores are acknowledged under the next layer's conv: what remains exposed is the
+//     publish phase's one batch of factor gathers and the neighbours' edge columns
+//
 //   * after the last layer the skip head (skip_projection, ReLU, output_projection) and the sampler's post-scaling run
 //     in the same launch (persist_tail.h): the skip sum never leaves the chip.
 //
-// Every workgroup must be resident: the launcher keeps the grid <= the CU count (one 512-thread, 139-KB-LDS workgroup
+// Every workgroup must be resident: the launcher keeps the grid <= the CU count (one 512-thread, 143-KB-LDS workgroup
 // per CU) and splits larger batches into balanced utterance chunks; spins are bounded and report through a timeout word.
 // Arithmetic and accumulation order are those of resblock_fused.hip: BITWISE equal to the per-layer kernels
 // (tests/test_gpu_parity.py::test_persistent_denoiser_bitwise).
@@ -58,8 +64,11 @@ constexpr int RING = 6;         // register ring depth of the weight stream (k-g
 constexpr int FN = 64;
 constexpr int NT = FN / 32;
 constexpr int U_LD = FN + 4;
-constexpr int IDX_LDS_BYTES = (FN + 2) * 2 * 4 + NW * 64 * 4 + NW * 4;      // behind the u / z buffers: FACT's (phoneme, pitch bucket) table of frames t0 - 1 .. t0 + FN, and
-                                                                   // 64 floats per wave to turn its two edge columns into ONE 64-lane granule store
+constexpr int ROWV = 4 * 32;    // per wave: the layer's row vectors of its 32 rows — bo (x half), bo (skip half), d, the next layer's dp
+constexpr int IDX_LDS_BYTES = (FN + 2) * 2 * 4 + NW * 64 * 4 + NW * 4 + NW * ROWV * 4;      // behind the u / z buffers: FACT's (phoneme, pitch bucket) table of frames t0 - 1 .. t0 + FN,
+                                                                   // 64 floats per wave to turn its two edge columns into ONE 64-lane granule store, the z flags,
+                                                                   // and the row vectors (16-byte aligned: the epilogue reads them as ds_read_b128)
+static_assert(((FN + 2) * 2 * 4 + NW * 64 * 4 + NW * 4) % 16 == 0, "row vectors are read 16 bytes at a time");
 constexpr unsigned SPIN_LIMIT = 1u << 20;     // bounded wait for a neighbour (~2 s); then the timeout word is set and
                                               // this wave stops waiting for the rest of the launch (results invalid)
 
@@ -212,6 +221,9 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
     // projection waits for, k-block by k-block, instead of a workgroup barrier (phase C)
     int* zflag = idx_lds + (FN + 2) * 2 + NW * 64;
     if (tid < NW) zflag[tid] = 0;
+    // the layer constants of this wave's 32 rows (epilogue: bo, d; publish: the next layer's dp), written and read by this wave alone
+    float* rowv = reinterpret_cast<float*>(zflag + NW) + w * ROWV;
+    constexpr bool ROWV_LDS = WINO != 0;
     if (FACT && tid < FN + 2) {
         int ph, ix;
         frame_idx(min(max(t0 - 1 + tid, 0), T - 1), ph, ix);
@@ -273,14 +285,20 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
 #else
     constexpr bool PUBS = false;
 #endif
+    // nine slots per wave: 0..7 the middle layer's, 8 = the NEXT layer's slot 0 (its arrival at barrier (1)), so that 7 -> 8 is the segment behind
+    // the last stamp of the publish phase and 0 -> 8 the layer period
+    constexpr int DBG_SLOTS = 9;
     auto stamp = [&](int l, int slot) {
-        if (DBG && !(PUBS && slot < 6) && a.dbg && l == a.NL / 2 && lane == 0)
-            a.dbg[((long)bid_dbg * NW + w) * 8 + slot] = (long long)__builtin_readcyclecounter();
+        if (DBG && a.dbg && lane == 0) {
+            long long* d = a.dbg + ((long)bid_dbg * NW + w) * DBG_SLOTS;
+            if (l == a.NL / 2 && !(PUBS && slot < 6)) d[slot] = (long long)__builtin_readcyclecounter();
+            if (l == a.NL / 2 + 1 && slot == 0) d[8] = (long long)__builtin_readcyclecounter();
+        }
     };
     auto pstamp = [&](int l, int slot) {
         if (DBG && PUBS && a.dbg && l == a.NL / 2 && lane == 0) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            a.dbg[((long)bid_dbg * NW + w) * 8 + slot] = (long long)__builtin_readcyclecounter();
+            a.dbg[((long)bid_dbg * NW + w) * DBG_SLOTS + slot] = (long long)__builtin_readcyclecounter();
         }
     };
     bool gave_up = false;
@@ -639,6 +657,24 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
             }
 #endif
         }
+        // the layer's row vectors of this wave's rows: two dwords per lane (lanes 0-31: bo's x half and d, lanes 32-63: bo's skip half and the next
+        // layer's dp), requested behind the projection ring's first groups like the residual stream above, handed to LDS after the first ring round
+        // (loads return in order: landed by then) and read back in the accumulator row order by the epilogue and the publish phase — as global
+        // loads behind the projection loop they were a whole L2 round trip, with every wave of the chip asking at once, in front of the first add.
+        // (The Winograd instances only: the direct form keeps x resident and has no register to carry the two across the first ring round.)
+        float rv0 = 0.f, rv1 = 0.f;
+        if constexpr (ROWV_LDS) {
+            const int ln = opaque(lane), row = mrow0 + (ln & 31);
+            rv0 = ldg(a.bo[l], (unsigned)((ln >> 5) * C + row));
+            rv1 = ldg((ln >> 5) && more ? dp_b + (long)(l + 1) * C : dv_b + (long)l * C, (unsigned)row);
+        }
+        auto stash_rowv = [&]() {
+            if constexpr (ROWV_LDS) {
+                const int ln = opaque(lane);
+                rowv[ln] = rv0;
+                rowv[64 + ln] = rv1;
+            }
+        };
         stamp(l, 3);
         // (3) no barrier here since round 5.  The two waves of a SIMD do not finish the conv together (the older one is served first: 87 k
         // against 116 k cycles, -DDBG stamps), and behind a barrier the early wave idled ~27 k cycles per layer while the late one ran the
@@ -671,7 +707,7 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
             // Round 5: no VALU address arithmetic in this loop either — the weights through a buffer descriptor (lane offset constant, k-group
             // offset scalar; groups past the end are out of range and read as zeros: no clamps), z through one LDS pointer per ring round
             // with immediate offsets.  The ring's look-ahead reads k-groups 32 .. 36 of z: up to 40 rows (~10.9 KB) past the z tile, of which only the
-            // index table (2.6 KB) lies inside the workgroup's allocation — the rest is beyond it.  Those reads are never USED (the groups do
+            // index table, the edge scratch and the row vectors (6.7 KB) lie inside the workgroup's allocation — the rest is beyond it.  Those reads are never USED (the groups do
             // not exist: `it + s < NG` guards the MFMAs), and an LDS read beyond the workgroup's allocation is bounds-checked by the hardware and returns
             // zero; clamping them costs a v_min per read in the loop next to fp32 MFMAs, where every VALU instruction is issue time (0.25 % per instruction)
             const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Wof[l]), 0, NG * (2 * C / 32) * 256 * 4, 0x00020000);
@@ -708,12 +744,14 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
             };
             if (more) {
                 ring_round(0, first_t{}, std::integral_constant<int, 0>{});
+                stash_rowv();
 #pragma unroll 1
                 for (int it = RING; it < NG; it += RING) ring_round(it, later_t{}, std::integral_constant<int, 0>{});
             } else {      // the last layer: only the skip half of the projection (its x' has no reader): half of this loop's MFMAs, 0.6 % of a launch
 #pragma unroll
                 for (int j = 0; j < NT; ++j) acc[0][j] = zero16;
                 ring_round(0, first_t{}, std::integral_constant<int, 1>{});
+                stash_rowv();
 #pragma unroll 1
                 for (int it = RING; it < NG; it += RING) ring_round(it, later_t{}, std::integral_constant<int, 1>{});
             }
@@ -721,15 +759,28 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
         stamp(l, 5);
         // ---- epilogue in registers: tile 0: x' = (o[:C] + (x + d)) / sqrt(2); tile 1: skip (+)= o[C:]
         {
-            const float* bo = a.bo[l];
-            const float* dl = dv_b + (long)l * C;
             const int ln = opaque(lane);
             float bor[MT][16], ddr[16];
+            if constexpr (ROWV_LDS) {
+                // bo and d of this wave's rows from its row vectors in LDS: rows 8 q + 4 khalf + {0, 1, 2, 3} = accumulator registers 4 q .. 4 q + 3
+                const float* rvk = rowv + 4 * (ln >> 5);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {            // all loads in flight before the first use
-                bor[0][r] = ldg(bo, (unsigned)(mrow0 + acc_row(r, ln)));
-                bor[1][r] = ldg(bo, (unsigned)(C + mrow0 + acc_row(r, ln)));
-                ddr[r] = ldg(dl, (unsigned)(mrow0 + acc_row(r, ln)));
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 b0 = *reinterpret_cast<const f32x4*>(rvk + 8 * q);
+                    const f32x4 b1 = *reinterpret_cast<const f32x4*>(rvk + 32 + 8 * q);
+                    const f32x4 dd = *reinterpret_cast<const f32x4*>(rvk + 64 + 8 * q);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { bor[0][4 * q + e] = b0[e]; bor[1][4 * q + e] = b1[e]; ddr[4 * q + e] = dd[e]; }
+                }
+            } else {
+                const float* bo = a.bo[l];
+                const float* dl = dv_b + (long)l * C;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {            // all loads in flight before the first use
+                    bor[0][r] = ldg(bo, (unsigned)(mrow0 + acc_row(r, ln)));
+                    bor[1][r] = ldg(bo, (unsigned)(C + mrow0 + acc_row(r, ln)));
+                    ddr[r] = ldg(dl, (unsigned)(mrow0 + acc_row(r, ln)));
+                }
             }
             // WINO: eight accumulators leave the conv loop no room for all 64 registers of state: the skip sum stays resident, the residual
             // stream x waits in memory (`xst`: L2 / Infinity Cache resident) between layers — read-modify-write by the lane that owns
@@ -745,6 +796,12 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
                     const float os = acc[1][j][r] + bor[1][r];
                     st[1][j][r] = l > 0 ? os + st[1][j][r] : os;
                 }
+            // the skip sum is formed HERE: left to the compiler the update sank into the loop latch, behind the publish phase and the x' stores,
+            // and took the wait for bo's skip half with it — a vmcnt(0) that also waited for the acknowledgement of those stores in front of barrier (1)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(st[1][j][r]));
         }
         if (!more) break;
         stamp(l, 6);
@@ -787,6 +844,9 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
             if (FACT) { hph = idx_lds[2 * (hside ? FN + 1 : 0)]; hix = idx_lds[2 * (hside ? FN + 1 : 0) + 1]; }   // (its two gathers ride with the wave's below)
             else hcp = (cp_b + (long)(l + 1) * C * T)[(unsigned)(hm * T + thc)];
         }
+        // (dp of the entry's row rides with them: loaded behind the neighbour wait it was a whole L2 round trip for one value between
+        //  "halo arrived" and barrier (1))
+        const float hdp = ldg(dpn, (unsigned)hm);
         unsigned long long hv = __hip_atomic_load((gu64*)hg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         pstamp(l, 1);
         // ---- next layer's u rows of this wave: cp (L2-warm, accumulator layout) + (x' + dp)
@@ -797,7 +857,8 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
             float dpr[16];
             if constexpr (FACT) {
                 // Round 5: every load of this phase is ISSUED BY HAND before the first wait — the frame indices of both n-tiles and of the
-                // halo frame first (one round trip), then the wave's 64 gathers, the halo entry's two and the 16 per-row dp values (one more).
+                // halo frame first (one round trip), then the wave's 64 gathers, the halo entry's two and the 16 per-row dp values (one more; round 7: the Winograd
+                // instances read dp from the wave's row vectors in LDS instead).
                 // Left to the compiler (at 253 of 256 registers) every element became mad_i64 / shift / add / load / s_waitcnt vmcnt(0): 32
                 // dependent L2 round trips per wave and layer, then the index loads of the second n-tile behind the first tile's gathers, then
                 // the dp loads one by one between the LDS stores — most of the publish phase's 15-20 k cycles.  The byte offset of an element
@@ -823,7 +884,6 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
                 const __amdgpu_buffer_rsrc_t r2t = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p2tl), 0, a.ld2 * C * 4, 0x00020000);
                 const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p1l), 0, C * ldp * 4, 0x00020000);
                 const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p2l), 0, C * a.ld2 * 4, 0x00020000);
-                const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dpn), 0, C * 4, 0x00020000);
                 f32x4 g1[NT][4], g2[NT][4];
                 const float h1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r1, (int)((unsigned)(hm * ldp + (hph > 0 ? hph - 1 : 0)) * 4u), 0, 0));
                 const float h2 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r2, (int)((unsigned)(hm * a.ld2 + hix) * 4u), 0, 0));
@@ -837,7 +897,8 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
                         g2[j][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r2t, o2 + q * 32, 0, 0));
                     }
                 }
-                {
+                if constexpr (!ROWV_LDS) {
+                    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dpn), 0, C * 4, 0x00020000);
                     const int od = (int)((unsigned)(mrow0 + 4 * (ln >> 5)) * 4u);
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
@@ -859,8 +920,18 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
 #pragma unroll
                     for (int r = 0; r < 16; ++r) cpc[j][r] = ldg(cpn, (unsigned)((mrow0 + acc_row(r, ln)) * T + t_c));
                 }
+                if constexpr (!ROWV_LDS) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) dpr[r] = ldg(dpn, (unsigned)(mrow0 + acc_row(r, ln)));
+                    for (int r = 0; r < 16; ++r) dpr[r] = ldg(dpn, (unsigned)(mrow0 + acc_row(r, ln)));
+                }
+            }
+            if constexpr (ROWV_LDS) {      // the next layer's dp of this wave's rows: from its row vectors
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 dq = *reinterpret_cast<const f32x4*>(rowv + 96 + 4 * (ln >> 5) + 8 * q);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dpr[4 * q + e] = dq[e];
+                }
             }
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
@@ -890,12 +961,14 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
             // after a timeout the halo column is poisoned: the utterance's mel comes out NaN (spreading one tile per layer) instead of
             // plausible-but-wrong, and cmtts_poll_error() reports the timeout
             const float xh = gave_up ? __builtin_nanf("") : (hinside ? __uint_as_float((unsigned)hv) : 0.f);
-            const float uh = hcp + (xh + dpn[hm]);
+            const float uh = hcp + (xh + hdp);
             u_lds[hm * U_LD + uidx(hside ? FN : -1)] = hinside ? uh : 0.f;
         }
         pstamp(l, 4);
         if constexpr (WINO) {      // x' goes back to memory LAST: in front of the publish phase's loads, every wait of that phase also waited for
-                                   // the acknowledgement of these stores (one counter for loads and stores)
+                                   // the acknowledgement of these stores (one counter for loads and stores).  Nothing behind them needs a vmcnt wait
+                                   // before barrier (1) (the skip sum is pinned in the epilogue): they are acknowledged under the next layer's conv,
+                                   // whose first ring wait orders them
             f32x4* px = reinterpret_cast<f32x4*>(pst_b) + (w * 8) * 64 + opaque(lane);
 #pragma unroll
             for (int j = 0; j < NT; ++j)
