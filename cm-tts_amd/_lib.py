@@ -87,6 +87,8 @@ SIGNATURES = {
     "cmtts_noise_fill_groups": (_i, [C.POINTER(NoiseGroupStruct), _i, _i, _i, _i, _vp]),
     "cmtts_sample_seeded_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "cmtts_sample_seeded": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _sz, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "cmtts_retake_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "cmtts_retake": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _sz, _vp]),
     "cmtts_sample_ragged": (_i, [_vp, C.POINTER(SampleGroupStruct), _i, _i, C.POINTER(_f), C.POINTER(_f), _i, _vp]),
     "cmtts_vocoder_create": (_i, [C.POINTER(_vp)]),
     "cmtts_vocoder_set_tensor": (_i, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i]),
@@ -294,6 +296,20 @@ def internal_noise_bits(seeds, B, T, M, first_draw, n_draws, t0, bits, stream):
         _noise_bits = C.CDLL(LIB_PATH).cmtts_internal_noise_bits
         _noise_bits.restype, _noise_bits.argtypes = _i, [_vp, _i, _i, _i, _i, _i, _i64, _vp, _vp]
     return _noise_bits(seeds, int(B), int(T), int(M), int(first_draw), int(n_draws), int(t0), bits, stream)
+
+
+_retake_step = None
+
+
+def internal_retake_step(x0, known, regen, seeds, windows, N, Tw, M, T, draw, scale, mode, out, stream):
+    """csrc/internal_hooks.h: cmtts_internal_retake_step — the masked sampler's step kernel alone on the caller's device buffers (tests
+    only; pointers as integers, c_void_p or None).  Returns the status."""
+    global _retake_step
+    load()
+    if _retake_step is None:
+        _retake_step = C.CDLL(LIB_PATH).cmtts_internal_retake_step
+        _retake_step.restype, _retake_step.argtypes = _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp]
+    return _retake_step(x0, known, regen, seeds, windows, int(N), int(Tw), int(M), int(T), int(draw), float(scale), int(mode), out, stream)
 
 
 _duration_fit = None

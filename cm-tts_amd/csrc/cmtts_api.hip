@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <map>
 #include <string>
 #include <vector>
@@ -29,6 +30,7 @@
 #include "resample.h"
 #include "loudness.h"
 #include "noise_philox.h"
+#include "retake.h"
 
 static thread_local std::string g_err;
 int fail(int code, const std::string& msg) {
@@ -1573,6 +1575,137 @@ int cmtts_sample_seeded(cmtts_model* m, const int64_t* seeds, const float* cond_
     cf.p1t = cond_p1 ? cond_p1t : nullptr;
     return sample_core(m, w, tail, (long)B * T * c.n_mels, cond_ct, speaker_emb, B, T, n_steps, sigmas, renoise_std, mel, (hipStream_t)stream,
                        cond_p1 ? &cf : nullptr, seeds);
+}
+
+// ---- re-taking spans of an utterance: the masked sampler on frame windows (retake.hip)
+}  // extern "C" (reopened below)
+namespace {
+// The denoiser workspace of the window batch (N, Tw), then the sampler's own buffers.
+struct RetakeWs {
+    DenWs den;
+    float *x0, *known, *cond, *spk;
+    int64_t* seeds;
+    uint8_t* regen;
+    StreamWindow* win;
+    size_t bytes;
+};
+RetakeWs carve_retake(const cmtts_config& c, int N, int Tw, void* base) {
+    RetakeWs r;
+    r.den = carve_den(c, N, Tw, base);
+    Carver cv(base);
+    cv.off = r.den.bytes;
+    const size_t nel = (size_t)N * Tw * c.n_mels;
+    r.x0 = cv.take<float>(nel);
+    r.known = cv.take<float>(nel);
+    r.cond = cv.take<float>((size_t)N * c.hidden * Tw);
+    r.spk = cv.take<float>((size_t)N * c.hidden);
+    r.seeds = cv.take<int64_t>((size_t)N);
+    r.regen = cv.take<uint8_t>((size_t)N * Tw);
+    r.win = cv.take<StreamWindow>((size_t)N);
+    r.bytes = cv.off + 256;
+    return r;
+}
+// Every window inside [0, T], every core inside its window, the cores of one utterance disjoint.
+bool retake_windows_ok(const int32_t* windows, int N, int B, int T, int Tw, std::string* why) {
+    std::vector<std::array<long, 3>> cores;      // (utterance, first frame, end)
+    for (int n = 0; n < N; ++n) {
+        const int32_t b = windows[4 * n], start = windows[4 * n + 1], off = windows[4 * n + 2], len = windows[4 * n + 3];
+        if (b < 0 || b >= B) { *why = "window " + std::to_string(n) + ": utterance out of range"; return false; }
+        if (start < 0 || (long)start + Tw > T) { *why = "window " + std::to_string(n) + " reaches outside [0, T]"; return false; }
+        if (off < 0 || len < 1 || (long)off + len > Tw) { *why = "window " + std::to_string(n) + ": core outside its window"; return false; }
+        cores.push_back({(long)b, (long)start + off, (long)start + off + len});
+    }
+    std::sort(cores.begin(), cores.end());
+    for (size_t k = 1; k < cores.size(); ++k)
+        if (cores[k][0] == cores[k - 1][0] && cores[k][1] < cores[k - 1][2]) {
+            *why = "two cores of utterance " + std::to_string(cores[k][0]) + " overlap";
+            return false;
+        }
+    return true;
+}
+}  // namespace
+extern "C" {
+
+size_t cmtts_retake_workspace_bytes(const cmtts_model* m, int N, int Tw) {
+    if (!m || N < 1 || Tw < 1) return 0;
+    return carve_retake(m->cfg, N, Tw, nullptr).bytes;
+}
+
+int cmtts_retake(cmtts_model* m, const float* mel_known, const uint8_t* regen, const float* cond_ct, const float* speaker_emb, const int64_t* seeds,
+                 int B, int T, const int32_t* windows, int N, int Tw, int n_steps, const float* sigmas, const float* renoise_std, float* mel_out,
+                 void* ws, size_t ws_bytes, void* stream) {
+    if (!m || !m->finalized) return fail(CMTTS_E_INVALID, "model not finalized");
+    if (!mel_known || !regen || !cond_ct || !seeds || !windows || !sigmas || !renoise_std || !mel_out || !ws || B < 1 || T < 1 || N < 1 || Tw < 1 ||
+        n_steps < 1)
+        return fail(CMTTS_E_INVALID, "cmtts_retake: bad argument");
+    const cmtts_config& c = m->cfg;
+    if (c.multi_speaker && !speaker_emb) return fail(CMTTS_E_INVALID, "cmtts_retake: speaker_emb is required for a multi-speaker model");
+    if (Tw > T) return fail(CMTTS_E_INVALID, "cmtts_retake: Tw > T");
+    for (int i = 0; i + 1 < n_steps; ++i)      // the kept frames of the next evaluation's input are known + noise at its sigma
+        if (!(renoise_std[i] >= 0.0f)) return fail(CMTTS_E_INVALID, "cmtts_retake: only the last evaluation may go without re-noising (renoise_std < 0)");
+    std::string why;
+    if (!retake_windows_ok(windows, N, B, T, Tw, &why)) return fail(CMTTS_E_INVALID, "cmtts_retake: " + why);
+    CHK(check_batch_invariant(m));
+    if (N > 65535) return fail(CMTTS_E_UNSUPPORTED, "cmtts_retake: N > 65535");
+    const RetakeWs w = carve_retake(c, N, Tw, ws);
+    if (ws_bytes < w.bytes) return fail(CMTTS_E_WORKSPACE, "retake workspace too small");
+    const DenWs& d = w.den;
+    const int M = c.n_mels;
+    hipStream_t s = (hipStream_t)stream;
+    // the window batch: everything is gathered before the first write to mel_out, which may be mel_known
+    HIPCHK(hipMemcpyAsync(w.win, windows, (size_t)N * sizeof(StreamWindow), hipMemcpyHostToDevice, s));
+    if (cmtts_launch_retake_gather(mel_known, regen, speaker_emb, seeds, w.win, N, T, Tw, M, c.hidden, w.known, w.regen, w.spk, w.seeds, (void*)s) != 0 ||
+        cmtts_launch_mel_window_gather(cond_ct, c.hidden, T, w.win, N, Tw, w.cond, (void*)s) != 0)
+        return fail(CMTTS_E_HIP, "cmtts_retake: gather launch failed");
+    if (mel_out != mel_known) HIPCHK(hipMemcpyAsync(mel_out, mel_known, (size_t)B * T * M * sizeof(float), hipMemcpyDeviceToDevice, s));
+    const float* spk = speaker_emb ? w.spk : nullptr;
+    // sample_core's loop on the [N, Tw] batch, the dense conditioner GEMM on the side stream
+    SideStream* ss = g_fused_resblock ? side_for(s) : nullptr;
+    if (ss) CHK(branch_fork(ss));
+    if (g_fused_resblock) CHK(cond_projections(m, d, w.cond, N, Tw, ss ? ss->side : s));
+    RetakeStepArgs st;
+    memset(&st, 0, sizeof(st));
+    st.x0 = w.x0; st.known = w.known; st.regen = w.regen; st.seeds = w.seeds; st.win = w.win;
+    st.N = N; st.Tw = Tw; st.M = M; st.T = T;
+    st.out = d.xcur; st.draw = 0; st.scale = c.sigma_max; st.mode = RETAKE_INIT;
+    if (cmtts_launch_retake_step(&st, (void*)s) != 0) return fail(CMTTS_E_HIP, "cmtts_retake: first-draw launch failed");
+    const float smin = c.sigma_min, sd2 = c.sigma_data * c.sigma_data;
+    for (int i = 0; i < n_steps; ++i) {
+        const float sg = sigmas[i];
+        const float dm = sg - smin;
+        const float c_skip = sd2 / (dm * dm + sd2);
+        const float rt = sqrtf(sg * sg + sd2);
+        const float c_out = dm * c.sigma_data / rt;
+        const float c_in = 1.0f / rt;
+        const float t_resc = 250.0f * logf(sg + 1e-44f);
+        const bool new_sigma = i == 0 || sigmas[i] != sigmas[i - 1];
+        const bool embed_side = i == 0 && ss != nullptr;
+        if (new_sigma) k_fill_float(d.tbuf, t_resc, N, embed_side ? ss->side : s);
+        if (embed_side) CHK(step_embedding(m, d, d.tbuf, spk, N, ss->side, t_resc));
+        const bool last = i + 1 == n_steps;
+        const MelPost post = {d.xcur, nullptr, c_out, c_skip, 0.0f, w.x0};      // x0 = c_out F + c_skip x, exactly as the plain sampler forms it
+        CHK(denoiser_core(m, d, d.xcur, c_in, d.tbuf, w.cond, spk, N, Tw, post, s, new_sigma && !embed_side, i == 0 ? ss : nullptr, t_resc));
+        st.draw = 1 + i; st.scale = renoise_std[i];
+        st.mode = last ? RETAKE_LAST : RETAKE_MID;
+        st.out = last ? mel_out : d.xcur;
+        if (cmtts_launch_retake_step(&st, (void*)s) != 0) return fail(CMTTS_E_HIP, "cmtts_retake: step launch failed");
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// Test hook (internal_hooks.h): retake_step_kernel alone on the caller's device buffers
+int cmtts_internal_retake_step(const float* x0, const float* known, const uint8_t* regen, const int64_t* seeds, const int32_t* windows, int N, int Tw,
+                               int M, int T, int draw, float scale, int mode, float* out, void* stream) {
+    if (!seeds || !windows || !out || N < 1 || Tw < 1 || M < 1 || T < Tw || draw < 0 || mode < RETAKE_INIT || mode > RETAKE_LAST ||
+        (mode != RETAKE_INIT && (!x0 || !regen)) || (mode == RETAKE_MID && !known))
+        return fail(CMTTS_E_INVALID, "cmtts_internal_retake_step: bad argument");
+    RetakeStepArgs st;
+    memset(&st, 0, sizeof(st));
+    st.x0 = x0; st.known = known; st.regen = regen; st.seeds = seeds; st.win = reinterpret_cast<const StreamWindow*>(windows);
+    st.N = N; st.Tw = Tw; st.M = M; st.T = T; st.out = out; st.draw = draw; st.scale = scale; st.mode = mode;
+    if (cmtts_launch_retake_step(&st, stream) != 0) return fail(CMTTS_E_HIP, "cmtts_internal_retake_step: launch failed");
+    return 0;
 }
 
 // karras_sample_tts for a RAGGED shard (BASELINE.json configs[3]: utterances dealt into static frame buckets): every group is a

@@ -50,6 +50,12 @@ int cmtts_internal_pack_weights(const char* layout, const float* kmajor, int tap
 // seg int32 [B][L] or NULL, target int32 [B][n_seg], unmet int32 [B] or NULL).  L up to 4096.
 int cmtts_internal_duration_fit(float* d_rounded, int* cum, int64_t* mel_len, const int64_t* src_lens, const int32_t* seg, const int32_t* target,
                                 int32_t* unmet, int B, int L, int n_seg, void* stream);
+// Test hook: retake_step_kernel alone (retake.hip; the one kernel between the evaluations of cmtts_retake) on the caller's device buffers.
+// mode 0: out [N][Tw][M] = scale * z(seeds[n], draw, windows[n].start + t, m); 1: out [N][Tw][M] = (regen ? x0 : known) + (z * scale) * 0.85f;
+// 2: out [B][T][M] (utterance windows[n].b, frame start + t) = x0 (+ (z * scale) * 0.85f when scale >= 0) where regen [N][Tw] is set, nothing
+// else written.  windows: DEVICE int32 [N][4] — NOT validated here (the caller's test does).
+int cmtts_internal_retake_step(const float* x0, const float* known, const uint8_t* regen, const int64_t* seeds, const int32_t* windows, int N, int Tw,
+                               int M, int T, int draw, float scale, int mode, float* out, void* stream);
 #ifdef __cplusplus
 }
 #endif

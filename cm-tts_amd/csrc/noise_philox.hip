@@ -25,45 +25,19 @@
 #include <stdint.h>
 
 #include "noise_philox.h"
+#include "noise_device.h"
 
 namespace {
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
-struct U4 {
-    uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0;
-        c1 = l1;
-        c2 = h0 ^ c3 ^ k1;
-        c3 = l0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return U4{c0, c1, c2, c3};
-}
-
-__device__ __forceinline__ void box_muller(uint32_t xa, uint32_t xb, float scale, float& za, float& zb) {
-    const float u1 = (float)((xa >> 8) + 1u) * 0x1p-24f;      // (0, 1], exact
-    const float u2x2 = (float)(xb >> 8) * 0x1p-23f;           // 2 u2 in [0, 2), exact
-    const float r = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincospif(u2x2, &sn, &cs);
-    const float a = r * cs, b = r * sn;
-    za = a * scale;      // the expression of scale_kernel (kernels.hip) on the rounded normal: the bits of a fill followed by k_scale
-    zb = b * scale;
-}
+using noise_dev::U4;
+using noise_dev::box_muller;
 
 // One block: frame t (tensor row), quad q of the row.  `row` = the tensor row's first float, `brow` = its first uint32 block word.
 template <bool VEC>
 __device__ __forceinline__ void emit_block(uint64_t seed, uint32_t draw, uint64_t j, int q, int M, float scale, float* row, uint32_t* brow) {
-    const U4 x = philox4x32_10((uint32_t)j, (uint32_t)(j >> 32), draw, 0x434D5454u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const U4 x = noise_dev::noise_block(seed, draw, j);
     if (brow) {
         *reinterpret_cast<uint4*>(brow + 4 * q) = make_uint4(x.x, x.y, x.z, x.w);
         return;

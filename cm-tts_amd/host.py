@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from . import noise as _noise
+from . import retake as _retake
 from .config import CMTTSConfig, HifiGanConfig
 
 
@@ -1498,6 +1499,122 @@ def phoneme_marks(out, T=None, sample_rate=None, vocoder=None):
         marks = torch.empty(B, L, 4, dtype=torch.int32, device=d.device)
         _lib.check(lib.cmtts_phoneme_marks(_ptr(d), _ptr(src), B, L, T, int(hop), int(up), int(down), _ptr(marks), _stream()))
     return marks
+
+
+# ----------------------------------------------------------------------------- re-taking spans
+
+def retake(model: CMTotalTTS, mel, cond_ct, speaker_emb, spans, seeds, n_steps=4, ts=None, steps=40, windowed=True):
+    """A new take of some frames of utterances that are already synthesized (cmtts_retake; the definition: retake.retake_reference).
+    mel [B,T,80]: the utterances as they are; spans: [(b, lo, hi)] half-open frame intervals to sample again; cond_ct [B,hidden,T],
+    speaker_emb: the conditioning the new take is drawn under; seeds: as in sample_with_cond (int64 [B] or one int) — a new seed
+    gives a new take.  Returns mel [B,T,80]: every frame outside the spans has the bits of `mel`, the frames inside are sampled
+    by the masked consistency sampler (the known frames are put back after every evaluation, so the take joins them).
+    n_steps evaluations on cmtts_schedule(n_steps); ts / steps give the general decreasing schedule of stochastic_iterative_sampler
+    instead (len(ts) - 1 evaluations).  windowed=True samples every cluster of spans on a window that reaches res_layers frames
+    beyond it (retake.plan_retake_windows) — the cost is the spans plus halos, not the utterances; windowed=False runs one
+    whole-utterance window per utterance with spans: the yardstick (the same bits in the direct conv form with the model option
+    "batch_invariant" set, within the conv forms' rounding otherwise).
+    Where spans come from: phoneme_marks(out)[b, l, 0:2] are the frames of phoneme l, and out["mel2ph"][b] == l + 1 marks the same
+    frames; a word is the union of its phonemes' intervals.  A changed prosody for the span (control tables of
+    DurationPitchSpeakerNet.forward, another speaker vector) gives a new cond_ct; pass segments= / target_frames= to that call so
+    that the span, and with it cond_ct, keeps its frame count — a retake does not change T."""
+    model._require()
+    lib, dev, cfg = model.lib, model.device, model.config
+    mel = _f32(mel, dev)
+    B, T, M = mel.shape
+    if M != cfg.n_mels or tuple(cond_ct.shape) != (B, cfg.hidden, T):
+        raise ValueError(f"retake: mel {tuple(mel.shape)} and cond_ct {tuple(cond_ct.shape)} do not fit [B,T,{cfg.n_mels}] / [B,{cfg.hidden},T]")
+    spans = [(int(b), int(lo), int(hi)) for b, lo, hi in spans]
+    mask = _retake.regen_mask(spans, B, T)
+    if ts is None:
+        sig = (C.c_float * n_steps)()
+        std = (C.c_float * n_steps)()
+        _lib.check(lib.cmtts_schedule(model._h, n_steps, sig, std))
+    else:
+        sg, sd_ = _retake.schedule_from_ts(ts, steps, cfg.sigma_min, cfg.sigma_max, cfg.rho)
+        n_steps = len(sg)
+        sig = (C.c_float * n_steps)(*sg.tolist())
+        std = (C.c_float * n_steps)(*sd_.tolist())
+    Tw, wins = _retake.plan_retake_windows(spans, T, cfg.res_layers) if windowed else _retake.whole_windows(spans, T)
+    tab = np.ascontiguousarray(np.asarray(wins, np.int32).reshape(-1, 4))
+    N = tab.shape[0]
+    cond_ct = _f32(cond_ct, dev)
+    spk = None if speaker_emb is None else _f32(speaker_emb, dev)
+    seeds = _device_seeds(seeds, B, dev)
+    with torch.cuda.device(dev):
+        regen = torch.from_numpy(mask.astype(np.uint8)).to(dev)
+        out = torch.empty_like(mel)
+        nb = lib.cmtts_retake_workspace_bytes(model._h, N, Tw)
+        ws = model._ws.get("retake", nb, dev)
+        _lib.check(lib.cmtts_retake(model._h, _ptr(mel), _ptr(regen), _ptr(cond_ct), _ptr(spk), _ptr(seeds), B, T, C.c_void_p(tab.ctypes.data),
+                                    N, Tw, n_steps, sig, std, _ptr(out), _ptr(ws), nb, _stream()))
+    return out
+
+
+def retake_pcm(mel_new, vocoder, pcm_old, spans, lengths=None, max_wav_value=32768.0, sample_rate=None, encoding="s16", gain_db=None):
+    """The audio of a retake without vocoding the utterances again: mel_new [B,80,T] (vocoder_infer's layout) is the mel after
+    retake(..., spans), pcm_old what vocoder_infer returned for the mel before it (a list of int16 arrays, or int16 [B, T * hop]).
+    Only the output frames retake.retake_pcm_range names — [lo - H, hi + H), H = the generator's receptive radius — are vocoded, in
+    windows that reach H frames beyond them (cmtts_vocoder_forward_windows, one call), and their int16 samples are spliced into a
+    copy of pcm_old.  Returns a list of int16 arrays like vocoder_infer's: every sample outside those frames has the bits of pcm_old,
+    and the whole equals vocoder_infer(mel_new, lengths=lengths) — bitwise in the direct conv form, within one LSB otherwise.
+    lengths: samples per utterance as in vocoder_infer (default: pcm_old's).  The native rate as int16 only."""
+    if sample_rate is not None or encoding != "s16" or gain_db is not None:
+        raise ValueError("retake_pcm: the native rate as int16 only (sample_rate, encoding and gain_db are not available here)")
+    vocoder._require()
+    lib, dev = vocoder.lib, vocoder.device
+    x = _f32(mel_new, dev)
+    B, M, T = x.shape
+    hop = vocoder.h.hop
+    H = lib.cmtts_vocoder_halo_frames(vocoder._h)
+    if H < 0:
+        _lib.check(H)
+    old = [np.asarray(w.cpu() if hasattr(w, "cpu") else w) for w in pcm_old]
+    if len(old) != B or any(w.dtype != np.int16 or w.ndim != 1 for w in old):
+        raise ValueError(f"retake_pcm: pcm_old must hold {B} int16 rows")
+    lens = [len(w) for w in old] if lengths is None else [int(n) for n in lengths]
+    if len(lens) != B or any(n > len(w) or n < 0 or n > T * hop for n, w in zip(lens, old)):
+        raise ValueError("retake_pcm: lengths do not fit pcm_old / the mel")
+    out = [w[:n].copy() for w, n in zip(old, lens)]
+    per = {}
+    for b, lo, hi in spans:
+        if not 0 <= int(b) < B:
+            raise ValueError(f"retake_pcm: span ({b}, {lo}, {hi}): utterance out of range")
+        per.setdefault(int(b), []).append(_retake.retake_pcm_range(lo, hi, H, T))
+    cores = []          # (b, first frame, end): the frame ranges of one utterance merged where they touch
+    for b in sorted(per):
+        for lo, hi in sorted(per[b]):
+            if cores and cores[-1][0] == b and lo <= cores[-1][2]:
+                cores[-1][2] = max(cores[-1][2], hi)
+            else:
+                cores.append([b, lo, hi])
+    if not cores:
+        return out
+    core = max(hi - lo for _, lo, hi in cores)
+    if core + 2 * H >= T:
+        Tw = core = T
+        wins = [(b, 0, lo, hi - lo) for b, lo, hi in cores]
+    else:
+        Tw = core + 2 * H
+        wins = []
+        for b, lo, hi in cores:
+            start = min(max(lo - H, 0), T - Tw)
+            wins.append((b, start, lo - start, hi - lo))
+    N = len(wins)
+    with torch.cuda.device(dev):
+        tab = torch.tensor(wins, dtype=torch.int32).pin_memory()      # read in place by the call: kept until the copy below has synchronised
+        pcm = torch.empty(N, core * hop, dtype=torch.int16, device=dev)
+        nb = lib.cmtts_vocoder_windows_workspace_bytes(vocoder._h, N, Tw)
+        ws = vocoder._ws.get("voc_stream", nb, dev)
+        _lib.check(lib.cmtts_vocoder_forward_windows(vocoder._h, _ptr(x), B, T, _ptr(tab), N, Tw, core, _ptr(pcm), float(max_wav_value),
+                                                     _ptr(ws), nb, _stream()))
+        arr = pcm.cpu().numpy()
+    check_async_error()
+    for n, (b, lo, hi) in enumerate(cores):
+        s0, s1 = lo * hop, min(hi * hop, lens[b])
+        if s1 > s0:
+            out[b][s0:s1] = arr[n, : s1 - s0]
+    return out
 
 
 def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=None, speakers=None, n_steps=4, noise=None,

@@ -325,6 +325,37 @@ int cmtts_sample_seeded(cmtts_model* m, const int64_t* seeds, const float* cond_
                         float* mel, void* ws, size_t ws_bytes, void* stream,
                         const float* cond_p1, const float* cond_p1t, int p1_ld, int L, const int64_t* mel2ph, const int64_t* p_idx);
 
+/* ---- re-taking spans of an utterance: the masked consistency sampler on frame windows (retake.hip; the
+ * definition in numpy: cmtts_amd/retake.py; the image form is the reference's iterative_inpainting, karras_diffusion.py:946-1003).
+ * Frames marked in `regen` are sampled again, every other frame of mel_known is KEPT: with z = the seeded noise of the utterance
+ * (cmtts_noise_fill's definition at the ABSOLUTE frame, so a window draws what the whole utterance would)
+ *   x  = sigma_max * z(draw 0)                                                      every frame, kept ones too
+ *   x0 = denoise(x, sigmas[i]); v = regen ? x0 : mel_known; x = v + (z(draw 1 + i) * renoise_std[i]) * 0.85f      i < n_steps - 1
+ *   last evaluation: mel_out = x0 (+ the same term when renoise_std[i] >= 0) on regenerated frames; kept frames are mel_known's
+ *   values verbatim — nothing is added to them (cmtts_schedule's last renoise_std is ~1e-10, not 0).
+ * Each operation is rounded to fp32, nothing is contracted; there is no clamp.  Only the last renoise_std may be negative.
+ * The denoiser's output at frame f depends on its input at frames f - res_layers .. f + res_layers only, and kept frames are reset
+ * after every evaluation, so the reach does not grow with n_steps: a span is sampled on a WINDOW of the utterance that reaches
+ * res_layers frames beyond it.  windows: HOST int32 [N][4] = (utterance b, window start, core_off, core_len), the table format of
+ * cmtts_vocoder_forward_windows: window n is frames [start, start + Tw) of utterance b; only regenerated frames inside its core
+ * [start + core_off, start + core_off + core_len) are sampled and written back, every other frame of the window is kept.  A core frame
+ * closer than res_layers to a window edge that is not 0 or T is computed against zero padding where the whole utterance has frames:
+ * keeping cores res_layers away from cut edges, and spans that interact in one core, is the planner's business
+ * (cmtts_amd/retake.py: plan_retake_windows).  Tw = T with start 0 is the whole-utterance form.
+ * The evaluations run the unchanged denoiser on the gathered [N, Tw] batch with the dense conditioner projections of the window's
+ * cond_ct; the seeded noise is drawn inside the one kernel between evaluations (no noise tensor).
+ * mel_known, mel_out fp32 [B,T,n_mels] (device): mel_out may BE mel_known (the known frames are gathered before anything is written);
+ * otherwise it first receives a device copy of mel_known (partly overlapping buffers are not supported).  regen: DEVICE uint8 [B,T].
+ * seeds: DEVICE int64 [B].  A pageable `windows` table is read before the call returns; a page-locked one is copied on `stream`.
+ * Validated on the host before anything is launched (CMTTS_E_INVALID, mel_out untouched): null pointers, B / T / N / Tw / n_steps
+ * < 1, Tw > T, b outside [0, B), a window outside [0, T], a core outside its window or empty, two cores of one utterance that overlap,
+ * a negative renoise_std before the last evaluation, no speaker_emb for a multi-speaker model.  A short workspace: CMTTS_E_WORKSPACE.
+ * ws: cmtts_retake_workspace_bytes(m, N, Tw) bytes (0 for N or Tw < 1). */
+size_t cmtts_retake_workspace_bytes(const cmtts_model* m, int N, int Tw);
+int cmtts_retake(cmtts_model* m, const float* mel_known, const uint8_t* regen, const float* cond_ct, const float* speaker_emb,
+                 const int64_t* seeds, int B, int T, const int32_t* windows, int N, int Tw, int n_steps,
+                 const float* sigmas_host, const float* renoise_std_host, float* mel_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the same sampler for a RAGGED shard (BASELINE.json configs[3]: variable-length utterances dealt into static frame buckets;
  * new work — the reference synthesizes one padded batch at a time, synthesize.py:195-227).  Every group is one padded (B, T) batch
  * with its own noise / conditioning / output / workspace (cmtts_denoiser_workspace_bytes(m, B, T)) exactly as cmtts_sample takes
