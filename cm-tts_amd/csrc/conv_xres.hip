@@ -410,7 +410,7 @@ __global__ __launch_bounds__(256, NT == 1 ? XRES_OCC1 : 1) void conv_xres_kernel
         // FFN fusion (model/blocks.py:539-551: w_2(gelu(w_1(x) * k^-0.5))): this workgroup's 128 activated rows are K segment `by` of the
         // linear that follows.  They go to LDS (over the X tile) instead of HBM, and the segment's partial product W2[:, 128 by : 128 by + 128] h
         // is formed here — two m-tiles per wave, the generic kernel's (16-row chunk, k) order over the segment => the bits of the
-        // K-segment launch it replaces (cmtts_api.hip: FFN2_SEG); reduce_partials_kernel adds the segments, bias, residual and mask as before.
+        // K-segment launch it replaces (text_side.hip: FFN2_SEG); reduce_partials_kernel adds the segments, bias, residual and mask as before.
         const int MT2 = a.M2 >> 5;                       // 8
         const float* w2 = a.w2frag + (((long)by * 16) * MT2 + 2 * w) * 256 + lane * 4;
         f32x4 A2[16][2];                                 // the wave's whole weight slice (32 KB), requested before the tile is even written

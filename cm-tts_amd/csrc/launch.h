@@ -1,5 +1,5 @@
-// What the host-side launch sequences (cmtts_api.hip: text, frame and denoiser side; vocoder.hip: the HiFi-GAN generator) share:
-// the generic conv's argument fill and launch, workspace carving, the library-owned side streams and the switch tables.
+// What the host-side launch sequences (cmtts_api.hip: denoiser and sampler side; text_side.hip: text and frame side; vocoder.hip: the HiFi-GAN
+// generator) share: the generic conv's argument fill and launch, workspace carving, the library-owned side streams and the switch tables.
 // Like fail() in model.h: declared here, defined once in cmtts_api.hip unless noted; small things are inline.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,6 +35,12 @@ struct SideStream {
 };
 SideStream* side_for(hipStream_t s);      // null: branch_streams is off or no stream could be had — the caller runs in line
 bool side2_ready(SideStream* ss);         // creates side2 / join2 / done0 / done1 on first use
+int branch_fork(SideStream* ss);          // work queued on ss->side after this sees everything queued on ss->user so far
+int branch_join(SideStream* ss);          // work queued on ss->user after this sees everything queued on ss->side so far
+
+int persist_blocks();                     // workgroups that are certainly co-resident: the CU count
+// The phoneme-level factor of the conditioner projections, p1 [B][res_layers * res_channels][Lp] = Wc * out1 (the frame side computes it beside its predictors)
+int cond_phoneme_factor(cmtts_model* m, const float* out1, int B, int Lp, float* p1, hipStream_t s);
 
 // Host copy of an int32 table that is device or page-locked host memory: a host table is read in place, a device table is read
 // back on `s`, which synchronises it.  *on_host tells which it was.  (vocoder.hip)
@@ -44,3 +50,4 @@ int fetch_table(const char* who, const void* table, void* host_copy, size_t byte
 struct Knob { const char* name; int* var; int lo, hi; };
 int knob_set(const Knob* tab, size_t n, const char* name, int value, bool* found);
 int vocoder_internal_set(const char* name, int value, bool* found);      // vocoder.hip: the generator's switches, asked first by cmtts_internal_set
+int text_internal_set(const char* name, int value, bool* found);         // text_side.hip: the FFT blocks', predictors' and frame side's switches, asked second

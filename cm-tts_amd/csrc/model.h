@@ -1,5 +1,5 @@
 // The model and vocoder handles of the C ABI (include/cmtts_hip.h) and what their weight import (import.hip) and their launch
-// sequences (cmtts_api.hip; the vocoder's: vocoder.hip; what those two share beyond the handles: launch.h) share: host tensors, packed convs, the device allocation list, the per-layer weight structs.
+// sequences (cmtts_api.hip; the text and frame side's: text_side.hip; the vocoder's: vocoder.hip; what those three share beyond the handles: launch.h) share: host tensors, packed convs, the device allocation list, the per-layer weight structs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

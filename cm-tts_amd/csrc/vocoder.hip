@@ -1,6 +1,6 @@
 // The HiFi-GAN vocoder's host side: the vocoder entry points of the C ABI (include/cmtts_hip.h) and the generator's launch sequence —
 // per stage an upsampler and three ResBlocks (hifigan/models.py:149-165), each ResBlock in the first form that takes its shape.
-// Weight import: import.hip; handle: model.h; what this unit shares with cmtts_api.hip: launch.h.
+// Weight import: import.hip; handle: model.h; what this unit shares with cmtts_api.hip and text_side.hip: launch.h.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>

@@ -267,7 +267,7 @@ def enc_sa_layer(sd, prefix, x, pad_mask, n_heads, kernel):
                                  sd[prefix + "self_attn.out_proj.weight"], pad_mask, n_heads)
     x = (x + h) * keep
     h = layer_norm(x, sd[prefix + "layer_norm2.weight"], sd[prefix + "layer_norm2.bias"], 1e-12)
-    qt = quant16 if _TEXT16 else (lambda a: a)          # "text16": the two FFN contractions take 16-bit operands (csrc/cmtts_api.hip fft_stack)
+    qt = quant16 if _TEXT16 else (lambda a: a)          # "text16": the two FFN contractions take 16-bit operands (csrc/text_side.hip fft_stack)
     h = conv1d(qt(h.transpose(0, 2, 1).astype(F32)), qt(sd[prefix + "ffn.ffn_1.weight"]), sd[prefix + "ffn.ffn_1.bias"],
                padding=kernel // 2)
     h = gelu_erf(h * F32(kernel ** -0.5)).transpose(0, 2, 1)
