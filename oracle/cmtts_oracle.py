@@ -53,8 +53,9 @@ class operands16:
     """``with operands16("bf16"):`` restates the library's reduced-precision scheme (BASELINE.json configs[2]/[4];
     the reference has no such mode): the MFMA operands of the denoiser's residual-block convs (u, z, the conditioner input and the three
     weight sets) and of the HiFi-GAN ResBlock convs (leaky_relu(x), leaky_relu(xt), weights) are rounded to 16 bits
-    (round-to-nearest-even from their fp32 value), products and sums stay in the working precision, and everything
-    else (biases, gate, residual arithmetic, conv_pre / transposed convs / conv_post) is untouched."""
+    (round-to-nearest-even from their fp32 value), products and sums stay in the working precision.  In "bf16" and "fp16"
+    hifigan_generator rounds the operands of the transposed convs (the upsamplers: leaky_relu(x), weights) as well; "fp16x3"
+    leaves them alone.  Everything else (biases, gate, residual arithmetic, conv_pre / conv_post) is untouched."""
 
     def __init__(self, mode, text=False):
         assert mode in (None, "fp32", "bf16", "fp16", "fp16x3")

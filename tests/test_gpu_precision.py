@@ -7,7 +7,7 @@ The reference computes in fp32 only, so 16-bit MFMA operands have no reference o
     ResBlocks rounded to 16 bits from their fp32 value, everything else untouched) and runs it in float64
     (`O.precision("f64")`).  Its distance from the plain float64 result is the SCHEME's error: a property of the
     precision choice (about ten unit roundoffs of the type on |mel| ~ 0.3), not of the implementation.
-  * SHALLOW paths (one residual layer; the vocoder, depth 24): the HIP result must match the 16-bit-operand oracle.  The
+  * SHALLOW paths (one residual layer): the HIP result must match the 16-bit-operand oracle.  The
     only differences left are fp32 accumulation order (bounded by the fp32 tests) and operands whose fp32 value sits so
     close to a 16-bit rounding boundary that the HIP path's fp32 drift `d` (relative, measured in the same test
     against float64) puts them into the neighbouring 16-bit value: an operand flips with probability ~ d / u16 and
@@ -18,13 +18,16 @@ The reference computes in fp32 only, so 16-bit MFMA operands have no reference o
         max <= max(5 x that, half of the scheme's own worst element)   (a flipped operand = one product off by a full ulp)
 
     with u16 the unit roundoff (2^-8 bf16, 2^-11 fp16), d32 = rms(hip32 - f64) / rms(f64), SAFETY = 4 (the model is an
-    order-of-magnitude estimate; measured on MI355X: 2.2x the model for the vocoder).
-  * DEEP paths (20 layers x T steps = 40-160 convs): every flipped operand perturbs the next layer's operands by a
+    order-of-magnitude estimate).
+  * DEEP paths (20 layers x T steps = 40-160 convs; the vocoder, 28 contractions deep since its upsamplers carry 16-bit
+    operands too: `check_ladder(..., deep=True)`): every flipped operand perturbs the next layer's operands by a
     fraction of a 16-bit ulp, which flips more of them — after a few layers the HIP run and the oracle run are two
     independent realisations of the same rounding noise (measured: rms(hip16 - oracle16) ~ rms(oracle16 - f64)), so
     an element-wise match is not a meaningful criterion.  What is: the HIP result is no farther from float64 than the
     scheme itself, in rms (x 1.3) and in max (x 1.6: two draws of a 5-sigma extreme), i.e. the implementation adds
     nothing to the scheme's own rounding noise; and the fp32 result stays as close to float64 as the reference's.
+    The vocoder's ELEMENT-WISE check is tests/test_gpu_vocoder_kernels.py: every one of its kernels alone against
+    float64 on rounded operands (the denoiser's counterpart is test_precision_one_residual_layer here).
 """
 import numpy as np
 import pytest
