@@ -46,6 +46,11 @@ class SampleGroupStruct(C.Structure):
                 ("cond_p1", C.c_void_p), ("p1_ld", C.c_int32), ("L", C.c_int32), ("mel2ph", C.c_void_p), ("p_idx", C.c_void_p)]
 
 
+class StepPlanStruct(C.Structure):
+    """struct cmtts_step_plan (include/cmtts_hip.h): HOST arrays as void*."""
+    _fields_ = [("max_steps", C.c_int32), ("n_steps", C.c_void_p), ("sigmas", C.c_void_p), ("renoise_std", C.c_void_p)]
+
+
 class NoiseGroupStruct(C.Structure):
     """struct cmtts_noise_group (include/cmtts_hip.h)."""
     _fields_ = [("seeds", C.c_void_p), ("B", C.c_int32), ("T", C.c_int32), ("out", C.c_void_p)]
@@ -87,6 +92,8 @@ SIGNATURES = {
     "cmtts_noise_fill_groups": (_i, [C.POINTER(NoiseGroupStruct), _i, _i, _i, _i, _vp]),
     "cmtts_sample_seeded_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "cmtts_sample_seeded": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _sz, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "cmtts_sample_mixed_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "cmtts_sample_mixed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(StepPlanStruct), _vp, _vp, _sz, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "cmtts_retake_workspace_bytes": (_sz, [_vp, _i, _i]),
     "cmtts_retake": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _sz, _vp]),
     "cmtts_sample_ragged": (_i, [_vp, C.POINTER(SampleGroupStruct), _i, _i, C.POINTER(_f), C.POINTER(_f), _i, _vp]),
@@ -310,6 +317,19 @@ def internal_retake_step(x0, known, regen, seeds, windows, N, Tw, M, T, draw, sc
         _retake_step = C.CDLL(LIB_PATH).cmtts_internal_retake_step
         _retake_step.restype, _retake_step.argtypes = _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp]
     return _retake_step(x0, known, regen, seeds, windows, int(N), int(Tw), int(M), int(T), int(draw), float(scale), int(mode), out, stream)
+
+
+_sample_rows = None
+
+
+def internal_sample_rows():
+    """csrc/internal_hooks.h: cmtts_internal_sample_rows — the utterance-evaluations launched by the last sampler call (tests only)."""
+    global _sample_rows
+    load()
+    if _sample_rows is None:
+        _sample_rows = C.CDLL(LIB_PATH).cmtts_internal_sample_rows
+        _sample_rows.restype, _sample_rows.argtypes = C.c_long, []
+    return int(_sample_rows())
 
 
 _duration_fit = None

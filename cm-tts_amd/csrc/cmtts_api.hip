@@ -411,12 +411,15 @@ struct MelPost {
     const float* noise;
     float c_out, c_skip, nstd;
     float* out;
+    // cmtts_sample_mixed: the three scalars, the re-noise switch and the destination per utterance (persist_args.h: PostRow); null = the scalars
+    const PostRow* rows = nullptr;
+    float* out_final = nullptr;
 };
 
 // The part of an evaluation in front of the residual layers: c_in scaling + transpose + input projection (+ clearing of the persistent
 // kernel's halo granules) and the step embedding.  *halo_zeroed: the granules of this (B, T) batch have been cleared on `s`.
 int denoiser_prologue(cmtts_model* m, const DenWs& w, const float* x_src, float in_scale, const float* timesteps, const float* spk, int B,
-                      int T, hipStream_t s, bool embed, float t_host, bool* halo_zeroed) {
+                      int T, hipStream_t s, bool embed, float t_host, bool* halo_zeroed, const float* in_scale_b = nullptr) {
     const cmtts_config& c = m->cfg;
     const int C = c.res_channels, NL = c.res_layers, M = c.n_mels;
     const long cs = (long)C * T;
@@ -425,7 +428,7 @@ int denoiser_prologue(cmtts_model* m, const DenWs& w, const float* x_src, float 
     if (g_inproj_fused && m->in_proj_f) {   // c_in scaling + transpose + input projection (+ halo clearing) in one launch: same bits
         InProjArgs ia;
         memset(&ia, 0, sizeof(ia));
-        ia.x = x_src; ia.scale = in_scale; ia.wf = m->in_proj_f; ia.bias = m->in_proj.bias; ia.h = w.h;
+        ia.x = x_src; ia.scale = in_scale; ia.scale_b = in_scale_b; ia.wf = m->in_proj_f; ia.bias = m->in_proj.bias; ia.h = w.h;
         ia.B = B; ia.T = T; ia.M = M; ia.C = C;
         const bool persist_path = g_fused_resblock && g_persist && NL <= PERSIST_MAX_LAYERS;
         if (persist_path) { ia.zero = w.halo; ia.zero_f4 = (long)(cmtts_persist_halo_bytes(B, T) / 16); }
@@ -434,7 +437,7 @@ int denoiser_prologue(cmtts_model* m, const DenWs& w, const float* x_src, float 
         *halo_zeroed = rin == 0 && persist_path && cmtts_persist_halo_bytes(B, T) % 16 == 0;
     }
     if (rin != 0) {
-        k_mel_prep(x_src, nullptr, in_scale, w.hin, B, T, M, s);
+        k_mel_prep(x_src, in_scale_b, in_scale, w.hin, B, T, M, s);
         ConvArgs a = conv_args(m->in_proj, w.hin, T, T, (long)M * T, w.h, T, cs, T);
         a.out[0].act = ACT_RELU;   // relu(relu(.)) == relu(.), model/modules.py:575-577,624
         CHK(launch(a, EPI_PLAIN, B, s));
@@ -460,13 +463,14 @@ int check_batch_invariant(const cmtts_model* m) {
 int denoiser_core(cmtts_model* m, const DenWs& w, const float* x_src, float in_scale, const float* timesteps,
                   const float* cond_ct, const float* spk, int B, int T, const MelPost& post, hipStream_t s, bool embed = true,
                   SideStream* pending = nullptr, float t_host = NAN,    // pending: a side branch (the conditioner GEMM) to join before the layers
-                  const CondFactors* cfk = nullptr, bool* cp_ready = nullptr) {   // cfk: w.cp was NOT filled — the persistent kernel gathers the factors (FACT)
+                  const CondFactors* cfk = nullptr, bool* cp_ready = nullptr,     // cfk: w.cp was NOT filled — the persistent kernel gathers the factors (FACT)
+                  const float* in_scale_b = nullptr) {                            // device [B]: c_in per utterance in place of in_scale (cmtts_sample_mixed)
     CHK(check_device_flag(true));
     const cmtts_config& c = m->cfg;
     const int C = c.res_channels, NL = c.res_layers, M = c.n_mels;
     const long cs = (long)C * T;
     bool halo_zeroed = false;
-    CHK(denoiser_prologue(m, w, x_src, in_scale, timesteps, spk, B, T, s, embed, t_host, &halo_zeroed));
+    CHK(denoiser_prologue(m, w, x_src, in_scale, timesteps, spk, B, T, s, embed, t_host, &halo_zeroed, in_scale_b));
     if (pending) CHK(branch_join(pending));
     const float* dp = m->cfg.multi_speaker ? w.dp : w.dproj;
     const bool unfused = !g_fused_resblock;   // three-launch form of the residual block (A/B and bitwise tests)
@@ -494,6 +498,7 @@ int denoiser_core(cmtts_model* m, const DenWs& w, const float* x_src, float in_s
             pa.skip_div = (float)sqrt((double)NL); pa.n_mels = M;
             pa.xold = post.xold; pa.noise = post.noise; pa.c_out = post.c_out; pa.c_skip = post.c_skip; pa.nstd = post.nstd;
             pa.out = post.out;
+            pa.post_rows = post.rows; pa.out_final = post.out_final;
         }
         pa.wino = g_persist_wino && m->winograd && !prec && m->res[0].w3w && w.pst;
         if (pa.wino && g_persist_wino == 3 && m->winograd == 1 && m->res[0].w3w43) pa.wino = 3;     // F(4,3) (model option "winograd" = 2 keeps F(2,3))
@@ -599,7 +604,8 @@ int denoiser_core(cmtts_model* m, const DenWs& w, const float* x_src, float in_s
         ConvArgs b = conv_args(m->out_proj, halt, T, T, cs, w.hin, T, (long)M * T, T);
         CHK(launch(b, EPI_PLAIN, B, s));
     }
-    k_mel_post(w.hin, post.xold, post.noise, post.c_out, post.c_skip, post.nstd, post.out, B, T, M, g_tmo_host, s);
+    if (post.rows) k_mel_post_rows(w.hin, post.xold, post.noise, post.rows, post.out, post.out_final, B, T, M, g_tmo_host, s);
+    else k_mel_post(w.hin, post.xold, post.noise, post.c_out, post.c_skip, post.nstd, post.out, B, T, M, g_tmo_host, s);
     return 0;
 }
 
@@ -701,6 +707,24 @@ int cmtts_schedule(const cmtts_model* m, int n_steps, float* sigmas, float* reno
 
 }  // extern "C" (reopened below)
 namespace {
+// cmtts_sample_mixed (per-utterance schedules on a batch sorted by non-increasing step count): evaluation i runs on the prefix [0, Bi) with
+// the scalings of its rows in the device table (c_in [B], t [B], PostRow [B] per evaluation, uploaded once before the first launch).
+struct MixedEval {
+    int Bi;                   // utterances still evaluated: #{b : n_b > i}
+    const float* c_in;        // device [B]
+    const float* t;           // device [B]: the rescaled timestep of every row (rows that have left keep their last one)
+    const PostRow* rows;      // device [B]
+    bool embed;               // some active row's timestep differs from the one its step embedding holds
+    bool t_uniform;           // all active rows share t_host: cmtts_sample's step-embedding path, cached row included
+    float t_host;
+    bool renoise;             // some active row is re-noised after this evaluation
+};
+struct MixedPlan {
+    std::vector<MixedEval> ev;
+    int n_re = 0;             // re-noise draws 1 .. n_re are read
+};
+long g_sample_rows = 0;       // utterance-evaluations launched by the last sampler call (cmtts_internal_sample_rows)
+
 // The sampler on one padded (B, T) batch whose workspace is already carved.  noise_stride = elements between consecutive noise tensors
 // (B * T * n_mels for a whole batch; a sub-batch [b0, b0 + B) of a larger batch keeps the larger batch's stride).
 // seeds (cmtts_sample_seeded): device int64 [B] — x_T is generated straight into w.xcur (noise_philox.hip, draw 0 scaled by sigma_max:
@@ -708,9 +732,10 @@ namespace {
 // launch on the side stream, beside the conditioner branch.
 int sample_core(cmtts_model* m, const DenWs& w, const float* noise, long noise_stride, const float* cond_ct, const float* speaker_emb, int B,
                 int T, int n_steps, const float* sigmas, const float* renoise_std, float* mel, hipStream_t s, const CondFactors* cf = nullptr,
-                const int64_t* seeds = nullptr) {
+                const int64_t* seeds = nullptr, const MixedPlan* mx = nullptr) {      // mx: n_steps = its evaluations, sigmas / renoise_std unused
     const cmtts_config& c = m->cfg;
     const long nel = (long)B * T * c.n_mels;
+    g_sample_rows = 0;
     // once for all n_steps evaluations, on the side stream: joined before the first residual layer of the first evaluation
     SideStream* ss = g_fused_resblock ? side_for(s) : nullptr;
     if (ss) CHK(branch_fork(ss));
@@ -739,15 +764,31 @@ int sample_core(cmtts_model* m, const DenWs& w, const float* noise, long noise_s
     if (seeds) {
         renoise0 = noise;
         int n_re = 0;
-        for (int i = 0; i < n_steps; ++i)
+        for (int i = 0; i < n_steps && !mx; ++i)
             if (renoise_std[i] >= 0.0f) n_re = i + 1;
+        if (mx) n_re = mx->n_re;
         if (cmtts_launch_noise_fill(seeds, B, T, c.n_mels, 0, 1, 0, c.sigma_max, w.xcur, nullptr, (void*)s) != 0 ||
             (n_re && cmtts_launch_noise_fill(seeds, B, T, c.n_mels, 1, n_re, 0, 1.0f, const_cast<float*>(noise), nullptr, (void*)(ss ? ss->side : s)) != 0))
             return fail(CMTTS_E_HIP, "seeded noise launch failed");
     } else
         k_scale(noise, w.xcur, nel, c.sigma_max, s);        // x_T = randn * sigma_max (karras_diffusion.py:534)
     const float smin = c.sigma_min, sd2 = c.sigma_data * c.sigma_data;
-    for (int i = 0; i < n_steps; ++i) {
+    for (int i = 0; i < n_steps && mx; ++i) {
+        // per-utterance schedules: the same evaluation on the prefix of utterances that still have one to take — every buffer is batch-major,
+        // so the prefix is the same workspace with a smaller B.  The step embedding runs on all B rows (include/cmtts_hip.h: the K-slicing of
+        // its MLP is a function of the row count), on the side stream in front of the first evaluation as below.
+        const MixedEval& e = mx->ev[i];
+        if (e.embed) {
+            hipStream_t es = i == 0 && ss ? ss->side : s;
+            if (e.t_uniform) k_fill_float(w.tbuf, e.t_host, B, es);
+            CHK(step_embedding(m, w, e.t_uniform ? w.tbuf : e.t, speaker_emb, B, es, e.t_uniform ? e.t_host : NAN));
+        }
+        MelPost post = {w.xcur, e.renoise ? renoise0 + (long)i * noise_stride : nullptr, 0.0f, 0.0f, 0.0f, w.xcur};
+        post.rows = e.rows; post.out_final = mel;
+        CHK(denoiser_core(m, w, w.xcur, 1.0f, w.tbuf, cond_ct, speaker_emb, e.Bi, T, post, s, false, i == 0 ? ss : nullptr, NAN, cfk, &cp_ready, e.c_in));
+        g_sample_rows += e.Bi;
+    }
+    for (int i = 0; i < n_steps && !mx; ++i) {
         // get_scalings_for_boundary_condition in fp32 (karras_diffusion.py:87-102)
         const float sg = sigmas[i];
         const float dm = sg - smin;
@@ -767,6 +808,7 @@ int sample_core(cmtts_model* m, const DenWs& w, const float* noise, long noise_s
         const MelPost post = {w.xcur, renoise ? renoise0 + (long)i * noise_stride : nullptr, c_out, c_skip,
                               renoise ? renoise_std[i] : 0.0f, last ? mel : w.xcur};
         CHK(denoiser_core(m, w, w.xcur, c_in, w.tbuf, cond_ct, speaker_emb, B, T, post, s, new_sigma && !embed_side, i == 0 ? ss : nullptr, t_resc, cfk, &cp_ready));
+        g_sample_rows += B;
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -884,6 +926,116 @@ int cmtts_sample_seeded(cmtts_model* m, const int64_t* seeds, const float* cond_
     return sample_core(m, w, tail, (long)B * T * c.n_mels, cond_ct, speaker_emb, B, T, n_steps, sigmas, renoise_std, mel, (hipStream_t)stream,
                        cond_p1 ? &cf : nullptr, seeds);
 }
+
+// ---- mixed step counts in one batch (include/cmtts_hip.h; the definition: cmtts_amd/steps.py)
+// The seeded sampler's workspace (denoiser workspace, max_steps noise tensors), then the table: per evaluation c_in [B], t [B], PostRow [B].
+static size_t mixed_table_offset(const cmtts_config& c, int B, int T, int max_steps) {
+    return (seeded_tail_offset(c, B, T) + (size_t)max_steps * B * T * c.n_mels * sizeof(float) + 255) & ~(size_t)255;
+}
+static size_t mixed_eval_bytes(int B) { return (size_t)B * (2 * sizeof(float) + sizeof(PostRow)); }
+size_t cmtts_sample_mixed_workspace_bytes(const cmtts_model* m, int B, int T, int max_steps) {
+    if (!m || B < 1 || T < 1 || max_steps < 1) return 0;
+    return mixed_table_offset(m->cfg, B, T, max_steps) + (size_t)max_steps * mixed_eval_bytes(B) + 256;
+}
+
+int cmtts_sample_mixed(cmtts_model* m, const int64_t* seeds, const float* noise, const float* cond_ct, const float* speaker_emb, int B, int T,
+                       const cmtts_step_plan* plan, float* mel, void* ws, size_t ws_bytes, void* stream, const float* cond_p1,
+                       const float* cond_p1t, int p1_ld, int L, const int64_t* mel2ph, const int64_t* p_idx) {
+    if (!m || !m->finalized) return fail(CMTTS_E_INVALID, "model not finalized");
+    if (!cond_ct || !mel || !ws || !plan || !plan->n_steps || !plan->sigmas || !plan->renoise_std || B <= 0 || T <= 0 || plan->max_steps < 1)
+        return fail(CMTTS_E_INVALID, "cmtts_sample_mixed: bad argument");
+    if ((seeds != nullptr) == (noise != nullptr)) return fail(CMTTS_E_INVALID, "cmtts_sample_mixed: give seeds or noise (exactly one of them)");
+    if (cond_p1 && (!mel2ph || !p_idx || L <= 0 || p1_ld < L)) return fail(CMTTS_E_INVALID, "cmtts_sample_mixed: incomplete factors");
+    const cmtts_config& c = m->cfg;
+    if (c.multi_speaker && !speaker_emb) return fail(CMTTS_E_INVALID, "cmtts_sample_mixed: speaker_emb is required for a multi-speaker model");
+    const int NS = plan->max_steps;
+    const int32_t* ns = plan->n_steps;
+    if (ns[0] != NS) return fail(CMTTS_E_INVALID, "cmtts_sample_mixed: n_steps[0] != max_steps");
+    for (int b = 0; b < B; ++b) {
+        if (ns[b] < 1 || ns[b] > NS) return fail(CMTTS_E_INVALID, "cmtts_sample_mixed: n_steps[" + std::to_string(b) + "] outside [1, max_steps]");
+        if (b && ns[b] > ns[b - 1])
+            return fail(CMTTS_E_INVALID, "cmtts_sample_mixed: n_steps must be non-increasing (utterance " + std::to_string(b) +
+                                             "); sort the batch by step count first (cmtts_amd/steps.py: order)");
+        for (int i = 0; i < ns[b]; ++i) {
+            const float sg = plan->sigmas[(long)i * B + b];
+            if (!(sg > 0.0f) || !(sg <= 3.402823466e38f))
+                return fail(CMTTS_E_INVALID, "cmtts_sample_mixed: sigma of utterance " + std::to_string(b) + ", evaluation " + std::to_string(i) +
+                                                 " is not a finite positive number");
+            if (!(plan->renoise_std[(long)i * B + b] >= 0.0f) && i + 1 != ns[b])
+                return fail(CMTTS_E_INVALID, "cmtts_sample_mixed: only an utterance's last evaluation may go without re-noising (renoise_std < 0; utterance " +
+                                                 std::to_string(b) + ")");
+        }
+    }
+    CHK(check_batch_invariant(m));
+    if (seeds && B > 65535) return fail(CMTTS_E_UNSUPPORTED, "cmtts_sample_mixed: B > 65535");
+    if (ws_bytes < cmtts_sample_mixed_workspace_bytes(m, B, T, NS)) return fail(CMTTS_E_WORKSPACE, "mixed sampler workspace too small");
+    DenWs w = carve_den(c, B, T, ws);
+    const float* tail = reinterpret_cast<const float*>(static_cast<char*>(ws) + seeded_tail_offset(c, B, T));
+    const long per = (long)B * T * c.n_mels;
+    hipStream_t s = (hipStream_t)stream;
+    CondFactors cf;
+    cf.p1 = cond_p1; cf.ldp = p1_ld; cf.L = L; cf.mel2ph = mel2ph; cf.p_idx = p_idx;
+    cf.p1t = cond_p1 ? cond_p1t : nullptr;
+    // a uniform plan is the uniform sampler: same launches, same bits
+    bool uniform = ns[B - 1] == NS;
+    for (int i = 0; i < NS && uniform; ++i)
+        for (int b = 1; b < B && uniform; ++b) {
+            const float s0 = plan->renoise_std[(long)i * B], sb = plan->renoise_std[(long)i * B + b];
+            uniform = plan->sigmas[(long)i * B + b] == plan->sigmas[(long)i * B] && (s0 >= 0.0f ? sb == s0 : !(sb >= 0.0f));
+        }
+    if (uniform) {
+        std::vector<float> sg((size_t)NS), sd((size_t)NS);
+        for (int i = 0; i < NS; ++i) { sg[i] = plan->sigmas[(long)i * B]; sd[i] = plan->renoise_std[(long)i * B]; }
+        return sample_core(m, w, seeds ? tail : noise, per, cond_ct, speaker_emb, B, T, NS, sg.data(), sd.data(), mel, s, cond_p1 ? &cf : nullptr, seeds);
+    }
+    // the table: the scalings of every (evaluation, utterance) by sample_core's fp32 expressions, once
+    const size_t eb = mixed_eval_bytes(B);
+    std::vector<char> host((size_t)NS * eb);
+    char* dev = static_cast<char*>(ws) + mixed_table_offset(c, B, T, NS);
+    MixedPlan mx;
+    mx.ev.resize((size_t)NS);
+    std::vector<float> held((size_t)B, NAN);      // the timestep whose embedding row b of the workspace holds
+    const float smin = c.sigma_min, sd2 = c.sigma_data * c.sigma_data;
+    for (int i = 0; i < NS; ++i) {
+        float* c_in = reinterpret_cast<float*>(host.data() + (size_t)i * eb);
+        float* tt = c_in + B;
+        PostRow* rows = reinterpret_cast<PostRow*>(tt + B);
+        MixedEval& e = mx.ev[i];
+        e.Bi = 0; e.embed = false; e.t_uniform = true; e.renoise = false;
+        for (int b = 0; b < B; ++b) {
+            if (i >= ns[b]) {      // left: the row is not evaluated; its timestep stays a valid one for the full-batch step embedding
+                c_in[b] = 0.0f; tt[b] = held[b]; rows[b] = PostRow{0.0f, 0.0f, 0.0f, 0u};
+                continue;
+            }
+            // get_scalings_for_boundary_condition in fp32 (karras_diffusion.py:87-102)
+            const float sg = plan->sigmas[(long)i * B + b], nstd = plan->renoise_std[(long)i * B + b];
+            const float dm = sg - smin;
+            const float c_skip = sd2 / (dm * dm + sd2);
+            const float rt = sqrtf(sg * sg + sd2);
+            const float c_out = dm * c.sigma_data / rt;
+            c_in[b] = 1.0f / rt;
+            tt[b] = 250.0f * logf(sg + 1e-44f);
+            const bool renoise = nstd >= 0.0f;
+            rows[b] = PostRow{c_out, c_skip, renoise ? nstd : 0.0f, (renoise ? POSTROW_RENOISE : 0u) | (i + 1 == ns[b] ? POSTROW_FINAL : 0u)};
+            e.Bi = b + 1;
+            e.embed = e.embed || tt[b] != held[b];
+            e.t_uniform = e.t_uniform && tt[b] == tt[0];
+            e.renoise = e.renoise || renoise;
+            if (renoise) mx.n_re = i + 1;
+        }
+        e.t_host = tt[0];
+        if (e.embed)
+            for (int b = 0; b < B; ++b) held[b] = e.t_uniform ? e.t_host : tt[b];
+        e.c_in = reinterpret_cast<const float*>(dev + (size_t)i * eb);
+        e.t = e.c_in + B;
+        e.rows = reinterpret_cast<const PostRow*>(e.t + B);
+    }
+    HIPCHK(hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, s));
+    return sample_core(m, w, seeds ? tail : noise, per, cond_ct, speaker_emb, B, T, NS, nullptr, nullptr, mel, s, cond_p1 ? &cf : nullptr, seeds, &mx);
+}
+
+// Test hook (internal_hooks.h): utterance-evaluations launched by the last sampler call
+long cmtts_internal_sample_rows(void) { return g_sample_rows; }
 
 // ---- re-taking spans of an utterance: the masked sampler on frame windows (retake.hip)
 }  // extern "C" (reopened below)

@@ -986,7 +986,7 @@ __global__ __launch_bounds__(64 * NW, 2) void denoiser_persist_kernel(const Pers
 
     if (a.tail) {   // skip head + post-scaling in-kernel (persist_tail.h); the u buffer is free since barrier (3), z after barrier (A) inside
         persist_tail::run(a, smem, smem + C * U_LD, st[1], w, lane, b, t0, T, RAGGED ? a.grp[gi].xold : a.xold,
-                          RAGGED ? a.grp[gi].noise : a.noise, RAGGED ? a.grp[gi].out : a.out, Tc);
+                          RAGGED ? a.grp[gi].noise : a.noise, RAGGED ? a.grp[gi].out : a.out, Tc, !RAGGED);
     } else {   // ---- the skip sum leaves the chip once
         float* skip = (RAGGED ? a.grp[gi].skip : a.skip) + (long)b * C * T;
 #pragma unroll
@@ -1130,6 +1130,8 @@ extern "C" int cmtts_launch_denoiser_persist(const PersistArgs* a_in, int max_bl
             c.xold = a.xold ? a.xold + off : nullptr;
             c.noise = a.noise ? a.noise + off : nullptr;
             c.out = a.out + off;
+            if (a.post_rows) c.post_rows = a.post_rows + b0;
+            if (a.out_final) c.out_final = a.out_final + off;
         }
         const void* kfn = kfns[a.dbg ? 1 : 0][a.fact ? 1 : 0][wsel];
         void* params[] = {(void*)&c};

@@ -486,6 +486,8 @@ int launch_mode(const PersistArgs& a, int tiles, int max_blocks, hipStream_t str
             c.xold = a.xold ? a.xold + off : nullptr;
             c.noise = a.noise ? a.noise + off : nullptr;
             c.out = a.out + off;
+            if (a.post_rows) c.post_rows = a.post_rows + b0;
+            if (a.out_final) c.out_final = a.out_final + off;
         }
         if (cmtts_persist_cooperative(16 + MODE, tiles, nb)) {
             void* params[] = {(void*)&c};

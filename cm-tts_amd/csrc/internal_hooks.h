@@ -56,6 +56,9 @@ int cmtts_internal_duration_fit(float* d_rounded, int* cum, int64_t* mel_len, co
 // else written.  windows: DEVICE int32 [N][4] — NOT validated here (the caller's test does).
 int cmtts_internal_retake_step(const float* x0, const float* known, const uint8_t* regen, const int64_t* seeds, const int32_t* windows, int N, int Tw,
                                int M, int T, int draw, float scale, int mode, float* out, void* stream);
+// Test hook: the utterance-evaluations (sum over evaluations of the utterances they ran on) launched by the last sampler call of the process:
+// B * n_steps after a uniform call, sum(n_steps[b]) after cmtts_sample_mixed — finished utterances really left, seen without timing anything.
+long cmtts_internal_sample_rows(void);
 #ifdef __cplusplus
 }
 #endif

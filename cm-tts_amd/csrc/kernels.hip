@@ -6,6 +6,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "persist_args.h"
 
 namespace {
 
@@ -757,6 +758,27 @@ __global__ void mel_post_kernel(const float* F, const float* xold, const float* 
     if (flag && !(fabsf(v) <= 3.402823466e38f) && *(volatile unsigned*)flag == 0u) *(volatile unsigned*)flag = 2u;
 }
 
+// ---- the same with a row of scalings per utterance (cmtts_sample_mixed on the per-layer routes): rows[b].flags bit 0 = add the re-noise
+// term (not expressible as nstd = 0: -0.0f + 0 * 0.85f is +0.0f), bit 1 = this evaluation is the utterance's last and its rows go to
+// out_final.  The expressions are mel_post_kernel's, so equal values give equal bits.
+__global__ void mel_post_rows_kernel(const float* F, const float* xold, const float* noise, const PostRow* rows, float* out, float* out_final,
+                                     int T, int M, unsigned* flag) {
+    const int m = threadIdx.x;
+    const int t = blockIdx.x * blockDim.y + threadIdx.y;
+    const int b = blockIdx.y;
+    if (t >= T || m >= M) return;
+    const PostRow pr = rows[b];
+    const float c_out = pr.c_out, c_skip = pr.c_skip, nstd = pr.nstd;
+    if (!(pr.flags & POSTROW_RENOISE)) noise = nullptr;
+    float* dst = (pr.flags & POSTROW_FINAL) ? out_final : out;
+    const long o = ((long)b * T + t) * M + m;
+    float v = c_out * F[((long)b * M + m) * T + t];
+    if (xold) v += c_skip * xold[o];
+    if (noise) v += noise[o] * nstd * 0.85f;
+    dst[o] = v;
+    if (flag && !(fabsf(v) <= 3.402823466e38f) && *(volatile unsigned*)flag == 0u) *(volatile unsigned*)flag = 2u;
+}
+
 // ---- DiffusionEmbedding (model/blocks.py:633-640): [sin(t*w) | cos(t*w)]
 __global__ void diff_embed_kernel(const float* t, const float* omega, float* emb, int C) {
     const int c = threadIdx.x, b = blockIdx.x;
@@ -1063,6 +1085,11 @@ void k_mel_post(const float* F, const float* xold, const float* noise, float c_o
     const int ty = 256 / M > 0 ? 256 / M : 1;
     hipLaunchKernelGGL(mel_post_kernel, dim3(cdiv(T, ty), B), dim3(M, ty), 0, s, F, xold, noise, c_out, c_skip, nstd,
                        out, T, M, flag);
+}
+void k_mel_post_rows(const float* F, const float* xold, const float* noise, const PostRow* rows, float* out, float* out_final, int B, int T,
+                     int M, unsigned* flag, hipStream_t s) {
+    const int ty = 256 / M > 0 ? 256 / M : 1;
+    hipLaunchKernelGGL(mel_post_rows_kernel, dim3(cdiv(T, ty), B), dim3(M, ty), 0, s, F, xold, noise, rows, out, out_final, T, M, flag);
 }
 void k_diff_embed(const float* t, const float* omega, float* emb, int B, int C, hipStream_t s) {
     hipLaunchKernelGGL(diff_embed_kernel, dim3(B), dim3(C), 0, s, t, omega, emb, C);

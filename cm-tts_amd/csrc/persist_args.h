@@ -28,6 +28,15 @@ struct PersistGroup {
     float* xst;           // WINO instances: [B][tiles][16384] kernel-private state (the residual stream x of every tile between layers)
 };
 
+// Per-utterance post-scaling of the in-kernel tail and of mel_post_rows_kernel (kernels.hip): cmtts_sample_mixed, where the utterances of
+// one evaluation differ in sigma, in whether they are re-noised and in whether this evaluation is their last.
+struct PostRow {
+    float c_out, c_skip, nstd;
+    unsigned flags;       // bit 0: add the re-noise term; bit 1: the utterance's last evaluation — its rows go to out_final, not out
+};
+#define POSTROW_RENOISE 1u
+#define POSTROW_FINAL 2u
+
 struct PersistArgs {
     const float* x0;      // [B][256][T] input of layer 0 (input projection output)
     const float* cp;      // [B][NL*256][T] conditioner projections of all layers (batch stride cp_bstride)
@@ -57,6 +66,10 @@ struct PersistArgs {
     const float* noise;   // [B][T][n_mels] or null
     float c_out, c_skip, nstd;
     float* out;           // [B][T][n_mels]
+    // per-utterance form of the five fields above (persist_tail.h; the RAGGED instances ignore it): null = the launch scalars.  Pointers,
+    // not tables — this struct travels by value in the kernel arguments.
+    const PostRow* post_rows;   // device [B]
+    float* out_final;           // [B][T][n_mels]: where the rows of an utterance with POSTROW_FINAL go
     // FACT instances (round 4, fp32 kernel): cp[r][t] = (mel2ph[t] > 0 ? p1[r][mel2ph[t] - 1] : 0) + p2[r][pidx[t]] is formed where cp would be
     // read — the cp tensor is neither written (cond_expand_kernel) nor read (335 MB per launch at the bench shape); the same bits as
     // expanding first.  fact = 0: read cp.

@@ -23,11 +23,23 @@ __device__ __forceinline__ int pt_row(int r, int lane) { return (r & 3) + 8 * (r
 // xold / noise / out: the utterance batch's [B][T][n_mels] tensors (a.xold / a.noise / a.out, or a ragged group's); Tc: frames at and
 // beyond Tc are not stored (Tc = T unless the utterance is trimmed)
 // skip = TPW x PT_NT accumulator tiles, [i * PT_NT + j]
+// rows: take the post-scaling of utterance b from a.post_rows[b] when that table is given (cmtts_sample_mixed: the utterances of one launch
+// differ in sigma, re-noising and destination); false for the RAGGED instances, whose b is not an index into it.  b is workgroup-uniform: the
+// row's four words are requested in front of the skip staging, so that their latency hides behind it, and broadcast from one lane into
+// SGPRs behind barrier (A) (v_readfirstlane) — where the launch scalars live, which are used when there is no table; nothing else changes
+// for that case.  The re-noise flag is not the same as nstd = 0: fmaf(0, 0.85f, -0.0f) is +0.0f.
 template <int TPW = 1>
 __device__ __forceinline__ void run(const PersistArgs& a, float* u_lds, float* z_lds, const f32x16* skip, int w, int lane,
-                                    int b, int t0, int T, const float* xold, const float* noise, float* out, int Tc) {
+                                    int b, int t0, int T, const float* xold, const float* noise, float* out, int Tc, bool rows = true) {
     constexpr int C = PT_C, NT = PT_NT, U_LD = PT_LD, RING = PT_RING;
     const int l31 = lane & 31, khalf = lane >> 5;
+    const bool table = rows && a.post_rows != nullptr;
+    unsigned row_w[4] = {0u, 0u, 0u, 0u};
+    if (table) {
+        const unsigned* pr = reinterpret_cast<const unsigned*>(a.post_rows + b);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) row_w[i] = pr[i];
+    }
     auto opaque = [](int v) { return pt_opaque(v); };
     auto acc_row = [](int r, int ln) { return pt_row(r, ln); };
     auto ldg = [](const float* p, unsigned i) { return pt_ldg(p, i); };
@@ -44,6 +56,15 @@ __device__ __forceinline__ void run(const PersistArgs& a, float* u_lds, float* z
                     u_lds[((w * TPW + i) * 32 + acc_row(r, ln)) * U_LD + j * 32 + c31] = skip[i * NT + j][r] / a.skip_div;
     }
     __syncthreads();   // (A) skip tile staged; every wave has left the last output projection (z is free)
+    float c_out = a.c_out, c_skip = a.c_skip, nstd = a.nstd;
+    if (table) {
+        c_out = __uint_as_float(__builtin_amdgcn_readfirstlane(row_w[0]));
+        c_skip = __uint_as_float(__builtin_amdgcn_readfirstlane(row_w[1]));
+        nstd = __uint_as_float(__builtin_amdgcn_readfirstlane(row_w[2]));
+        const unsigned flags = __builtin_amdgcn_readfirstlane(row_w[3]);
+        if (!(flags & POSTROW_RENOISE)) noise = nullptr;
+        if (flags & POSTROW_FINAL) out = a.out_final;
+    }
     constexpr int NGC = C / 8;
     auto load_bt = [&](float (&dst)[4][NT], const float* src, int g) {
         const float* bs = src + (g * 8 + khalf) * U_LD + l31;
@@ -135,9 +156,9 @@ __device__ __forceinline__ void run(const PersistArgs& a, float* u_lds, float* z
                 const int m = mrow0 + acc_row(r, ln);
                 const bool ok = m < M && t < Tc;
                 const float F = h[j][r] + (m < M ? bi[r] : 0.f);
-                float v = a.c_out * F;
-                if (xold) v = __builtin_fmaf(a.c_skip, xo[r], v);
-                if (noise) v = __builtin_fmaf(nz[r] * a.nstd, 0.85f, v);
+                float v = c_out * F;
+                if (xold) v = __builtin_fmaf(c_skip, xo[r], v);
+                if (noise) v = __builtin_fmaf(nz[r] * nstd, 0.85f, v);
                 if (ok) out[ob + m] = v;
                 // a non-finite mel value (16-bit operands beyond the fp16 range, non-finite weights / inputs) is reported, not just returned
                 bad |= ok && !(fabsf(v) <= 3.402823466e38f);

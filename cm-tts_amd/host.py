@@ -747,8 +747,103 @@ def synchronize(device=None):
     check_async_error()
 
 
+def _step_counts(n_steps, B, what):
+    """None for an int (the uniform call), else the per-utterance step counts as a list of B ints."""
+    if isinstance(n_steps, (int, np.integer)):
+        return None
+    if isinstance(n_steps, torch.Tensor):
+        n_steps = n_steps.cpu().tolist()
+    counts = [int(v) for v in n_steps]
+    if len(counts) != B:
+        raise ValueError(f"{what}: n_steps has {len(counts)} entries for a batch of {B}")
+    return counts
+
+
+def _take_rows(v, perm, B):
+    """v with its utterance rows in the order perm: a tensor / array whose first dimension is B or a list of B entries; anything else
+    (None, a number) as it is."""
+    if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == B:
+        return v[torch.as_tensor(perm, device=v.device)]
+    if isinstance(v, np.ndarray) and v.ndim >= 1 and v.shape[0] == B:
+        return v[np.asarray(perm)]
+    if isinstance(v, (list, tuple)) and len(v) == B:
+        return type(v)(v[int(k)] for k in perm)
+    return v
+
+
+def _text_level_order(counts, B, seeds, what):
+    """Per-utterance step counts of a text-level call: every count in {1, 2, 4}; returns (perm, inverse, sorted counts, seeds as a [B] array in the
+    caller's order or None) — steps.order's stable permutation into non-increasing counts, applied before the duration net."""
+    from . import steps as S
+    if any(n not in (1, 2, 4) for n in counts):
+        raise ValueError(f"{what}: every step count must be 1, 2 or 4 (synthesize.py:111-147), got {counts}")
+    perm = S.order(counts)
+    inv = np.argsort(perm, kind="stable")
+    if isinstance(seeds, (int, np.integer)):          # one int names utterance b's seed by its position in the CALLER's order
+        seeds = _noise.utterance_seeds(int(seeds), np.arange(int(B)))
+    return perm, inv, [counts[int(k)] for k in perm], seeds
+
+
+def sample_mixed(model: CMTotalTTS, cond_ct, speaker_emb, n_steps, noise=None, factors=None, seeds=None, sigmas=None, renoise_std=None,
+                 out=None):
+    """Per-utterance step counts in one batch (cmtts_sample_mixed; the definition: cmtts_amd/steps.py): utterance b takes n_steps[b]
+    evaluations and comes out with the bits of its row in sample_with_cond(n_steps=n_steps[b]) on the same batch, but an utterance
+    that has taken its last evaluation leaves — later evaluations run on the rest.  n_steps must be NON-INCREASING in b
+    (ValueError otherwise: sort the batch with steps.order first).  sigmas / renoise_std: float32 [max_steps, B] per-utterance
+    schedules (entry (i, b) is read where i < n_steps[b]; default: cmtts_schedule(n_steps[b]) per utterance).
+    noise: fp32 [n_noise,B,1,T,80] with n_noise = max_steps + 1 (max_steps = 1: 1), or seeds as in sample_with_cond.
+    out: a contiguous fp32 [B,T,80] device tensor to write (every row is written exactly once).  Returns mel [B,T,80]."""
+    from . import steps as S
+    model._require()
+    lib, dev, cfg = model.lib, model.device, model.config
+    B, H, T = cond_ct.shape
+    counts = _step_counts(n_steps, B, "sample_mixed")
+    if counts is None:
+        raise ValueError("sample_mixed: n_steps must be a sequence (one int: sample_with_cond)")
+    if (noise is None) == (seeds is None):
+        raise ValueError("sample_mixed: give noise or seeds (one of them)")
+    if (sigmas is None) != (renoise_std is None):
+        raise ValueError("sample_mixed: give sigmas and renoise_std together")
+    S.validate(counts)          # ValueError names steps.order
+    NS = counts[0]
+    if sigmas is None:
+        sig = np.zeros((NS, B), np.float32)
+        std = np.zeros((NS, B), np.float32)
+        for n in sorted(set(counts)):
+            a, d = (C.c_float * n)(), (C.c_float * n)()
+            _lib.check(lib.cmtts_schedule(model._h, n, a, d))
+            cols = [b for b in range(B) if counts[b] == n]
+            sig[:n, cols] = np.asarray(a[:], np.float32)[:, None]
+            std[:n, cols] = np.asarray(d[:], np.float32)[:, None]
+    else:
+        sig = np.ascontiguousarray(np.asarray(sigmas, np.float32))
+        std = np.ascontiguousarray(np.asarray(renoise_std, np.float32))
+        S.validate(counts, sig, std)
+    ns = np.asarray(counts, np.int32)
+    plan = _lib.StepPlanStruct(NS, ns.ctypes.data, sig.ctypes.data, std.ctypes.data)
+    if seeds is not None:
+        seeds = _device_seeds(seeds, B, dev)
+    else:
+        n_noise = 1 if not (std[np.arange(NS)[:, None] < ns[None, :]] >= 0).any() else NS + 1
+        assert noise.shape[0] >= n_noise and tuple(noise.shape[1:]) == (B, 1, T, cfg.n_mels)
+    with torch.cuda.device(dev):
+        mel = torch.empty(B, T, cfg.n_mels, dtype=torch.float32, device=dev) if out is None else out
+        if mel.dtype != torch.float32 or tuple(mel.shape) != (B, T, cfg.n_mels) or not mel.is_contiguous() or mel.device != torch.device(dev):
+            raise ValueError(f"sample_mixed: out must be a contiguous float32 [{B}, {T}, {cfg.n_mels}] tensor on {dev}")
+        nb = lib.cmtts_sample_mixed_workspace_bytes(model._h, B, T, NS)
+        ws = model._ws.get("den_mixed", nb, dev)
+        if factors is None:
+            factors = getattr(cond_ct, "_cmtts_factors", None)
+        f = factors if factors is not None and factors.matches(cond_ct) else None
+        _lib.check(lib.cmtts_sample_mixed(model._h, _ptr(seeds), _ptr(noise), _ptr(cond_ct), _ptr(speaker_emb), B, T, C.byref(plan),
+                                          _ptr(mel), _ptr(ws), nb, _stream(), _ptr(f.p1 if f else None), _ptr(f.p1t if f else None),
+                                          f.p1_ld if f else 0, f.L if f else 0, _ptr(f.mel2ph if f else None), _ptr(f.p_idx if f else None)))
+    return mel
+
+
 def sample_with_cond(model: CMTotalTTS, cond_ct, speaker_emb, n_steps, noise=None, factors=None, seeds=None):
     """T-step consistency sampling on precomputed conditioning (cmtts_sample).
+    n_steps: an int, or a sequence of B per-utterance step counts, non-increasing (sample_mixed: cmtts_sample_mixed).
     noise: fp32 [n_noise,B,1,T,80] on device.  factors: the duration net's out["cond_factors"] for THIS cond_ct (default: the ones the
     duration net attached to the tensor object it returned; the conditioner projections are then expanded from them,
     cmtts_sample_factored — an unmodified, same-storage cond_ct only, else the dense GEMM).  Returns mel [B,T,80].
@@ -758,6 +853,8 @@ def sample_with_cond(model: CMTotalTTS, cond_ct, speaker_emb, n_steps, noise=Non
     model._require()
     lib, dev, cfg = model.lib, model.device, model.config
     B, H, T = cond_ct.shape
+    if _step_counts(n_steps, B, "sample_with_cond") is not None:
+        return sample_mixed(model, cond_ct, speaker_emb, n_steps, noise, factors, seeds)
     n_noise = 1 if n_steps == 1 else n_steps + 1
     if (noise is None) == (seeds is None):
         raise ValueError("sample_with_cond: give noise or seeds (one of them)")
@@ -823,6 +920,9 @@ def sample_ragged(model: CMTotalTTS, groups, n_steps, tail_frames=0):
     stack and within fp32 rounding of it (<= 1.5e-5: include/cmtts_hip.h, tests/conftest.py WINO_TRIM_TOL; ~2e-6 typical) in the default F(4,3) form, whose frame quads round every output from all
     six inputs of the quad; frames beyond the computed range are zeros.
     Returns the list of mels [B,T,80]."""
+    if not isinstance(n_steps, (int, np.integer)):
+        raise NotImplementedError("sample_ragged: per-utterance step counts are not supported on a ragged shard (one int; "
+                                  "sample_with_cond takes a sequence on a padded batch)")
     model._require()
     lib, dev, cfg = model.lib, model.device, model.config
     n_noise = 1 if n_steps == 1 else n_steps + 1
@@ -1639,20 +1739,39 @@ def synthesize_stream(model: CMTotalTTS, vocoder, texts, src_lens, spker_embeds=
         raise ValueError("synthesize_stream: give noise or seeds, not both")
     if on_marks is not None and not callable(on_marks):
         raise ValueError("synthesize_stream: on_marks must be callable")
+    B0 = int(torch.as_tensor(texts).shape[0])
+    counts = _step_counts(n_steps, B0, "synthesize_stream")
+    perm = inv = None
+    if counts is not None:
+        # per-utterance step counts: the batch is sorted by step count at the text level (steps.order), sampled in one cmtts_sample_mixed call
+        # and handed out in the caller's order; given noise rows move with their utterances
+        perm, inv, n_steps, seeds = _text_level_order(counts, B0, seeds, "synthesize_stream")
+        texts, src_lens, spker_embeds, speakers, p_control, e_control, d_control, target_frames, segments, seeds = (
+            _take_rows(v, perm, B0) for v in (texts, src_lens, spker_embeds, speakers, p_control, e_control, d_control, target_frames,
+                                              segments, seeds))
     out = model.duration_pitch_energy_net(speakers=speakers, texts=texts, src_lens=src_lens, spker_embeds=spker_embeds,
                                           p_control=p_control, e_control=e_control, d_control=d_control,
                                           target_frames=target_frames, segments=segments)
     B, T, _ = out["cond"].shape
     cfg = model.config
-    if n_steps not in (1, 2, 4):
+    if counts is None and n_steps not in (1, 2, 4):
         raise ValueError("n_steps must be 1, 2 or 4 (synthesize.py:111-147)")
-    draws = 1 if n_steps == 1 else n_steps + 1
-    if noise is None and seeds is None:
+    most = n_steps if counts is None else n_steps[0]
+    draws = 1 if most == 1 else most + 1
+    if noise is None and seeds is None:      # drawn in the caller's order
         noise = _draw_sampler_noise(generator or DummyGenerator(), B, T, cfg.n_mels, draws, model.device)
+    if noise is not None and perm is not None:
+        noise = noise[:, torch.as_tensor(perm, device=noise.device)].contiguous()
     mel = sample_with_cond(model, out["cond_ct"], out["speaker_emb"], n_steps, noise, factors=out.get("cond_factors"), seeds=seeds)
     mel_lens = out["mel_lens"].cpu().tolist()
+    marks = phoneme_marks(out, sample_rate=sample_rate, vocoder=vocoder) if on_marks is not None else None
+    if inv is not None:
+        back = torch.as_tensor(inv, device=mel.device)
+        mel = mel[back].contiguous()
+        mel_lens = [mel_lens[int(k)] for k in inv]
+        marks = marks[back] if marks is not None else None
     if on_marks is not None:
-        on_marks(phoneme_marks(out, sample_rate=sample_rate, vocoder=vocoder).cpu().numpy())
+        on_marks(marks.cpu().numpy())
     yield from vocoder_infer_stream(mel.transpose(1, 2), vocoder, mel_lens, chunk_frames, max_wav_value, sample_rate=sample_rate,
                                     encoding=encoding, gain_db=gain_db)
 
@@ -2082,13 +2201,29 @@ class CMTotalTTSSynthesize:
         model.eval()
         return model, diffusion
 
-    def synthesize(self, batch, p_control=None, e_control=None, d_control=None, seeds=None, target_frames=None, segments=None):
+    def synthesize(self, batch, p_control=None, e_control=None, d_control=None, seeds=None, target_frames=None, segments=None, n_steps=None):
         """batch = (ids, raw_texts, speakers, texts, src_lens, max_src_len, spker_embeds) after to_device (:88-153).
         The controls given at construction apply (numbers, or float32 [B] / [B, L] tensors); a control given here replaces the
         constructor's for this call — a table on top of a constructor scalar other than 1 is a ValueError.
         seeds: int64 [B] utterance seeds or one int — the sampler generates the seeded noise itself (sample_with_cond) and the
         generator is not drawn from.  A "determ-indiv" generator (get_generator) without `seeds` does the same with its own seeds.
-        target_frames / segments: duration targets (DurationPitchSpeakerNet.forward) — out_put[11] are then the fitted lengths."""
+        target_frames / segments: duration targets (DurationPitchSpeakerNet.forward) — out_put[11] are then the fitted lengths.
+        n_steps: None = args.T; an int replaces it for this call; a sequence of B step counts (each 1, 2 or 4, any order) samples the
+        batch in ONE mixed call (cmtts_sample_mixed): the batch is sorted by step count at the text level (steps.order), every
+        utterance comes back at the caller's position with the bits of its row in the uniform call at its count, and noise drawn
+        from the generator is drawn in the caller's order."""
+        B0 = int(torch.as_tensor(batch[3]).shape[0])
+        counts = None if n_steps is None else _step_counts(n_steps, B0, "synthesize")
+        perm = inv = None
+        if counts is not None:
+            perm, inv, counts, seeds = _text_level_order(counts, B0, seeds, "synthesize")
+            p_control = self.p_control if p_control is None else p_control
+            e_control = self.e_control if e_control is None else e_control
+            d_control = self.d_control if d_control is None else d_control
+            batch = list(batch)
+            batch[2], batch[3], batch[4], batch[-1], p_control, e_control, d_control, target_frames, segments, seeds = (
+                _take_rows(v, perm, B0) for v in (batch[2], batch[3], batch[4], batch[-1], p_control, e_control, d_control, target_frames,
+                                                  segments, seeds))
         kw = {"speakers": batch[2], "texts": batch[3], "src_lens": batch[4], "spker_embeds": batch[-1]}
         if target_frames is not None or segments is not None:
             kw["target_frames"], kw["segments"] = target_frames, segments
@@ -2104,7 +2239,7 @@ class CMTotalTTSSynthesize:
         out_dict = self.duration_pitch_energy_net(**kw)
         B, T, _ = out_dict["cond"].shape
         cfg = self.model.config
-        steps = int(self.args.T)
+        steps = int(self.args.T) if n_steps is None else (counts[0] if counts is not None else int(n_steps))
         if steps == 1:
             n_steps, draws = 1, 1
         elif steps in (2, 4):
@@ -2118,6 +2253,8 @@ class CMTotalTTSSynthesize:
         gen = self.generator or DummyGenerator()
         if seeds is not None and not fusable:
             raise NotImplementedError("seeds: the fused sampler only (a distilled model with the config's sigmas)")
+        if counts is not None and not fusable:
+            raise NotImplementedError("n_steps per utterance: the fused sampler only (a distilled model with the config's sigmas)")
         if target_frames is not None and not fusable:      # the host-side loops re-run the duration net from the reference's argument list
             raise NotImplementedError("target_frames: the fused sampler only (a distilled model with the config's sigmas)")
         if not fusable:      # e.g. a progdist teacher: the reference's sampler loops, host-side (karras_sample_tts routes)
@@ -2128,17 +2265,26 @@ class CMTotalTTSSynthesize:
                                        ts=None if steps == 1 else (0,) * steps + (1,), generator=gen)
         else:                # the duration net ran once above; the reference's in-sampler re-runs are bit-identical
             noise = None
+            from_gen = False
             if seeds is None and isinstance(gen, IndivGenerator) and gen.draw == 0:
                 seeds = gen.seeds_for(B)          # the sampler makes draws 0 .. draws - 1 itself
+                from_gen = True
                 gen.draw += draws
             elif seeds is None:
                 noise = _draw_sampler_noise(gen, B, T, cfg.n_mels, draws, self.model.device)
-            sample = sample_with_cond(self.model, out_dict["cond_ct"], out_dict["speaker_emb"], n_steps, noise,
+            if perm is not None and seeds is None:      # drawn in the caller's order: the rows move with their utterances
+                noise = noise[:, torch.as_tensor(perm, device=noise.device)].contiguous()
+            elif perm is not None and from_gen:
+                seeds = _take_rows(np.asarray(seeds), perm, B)
+            sample = sample_with_cond(self.model, out_dict["cond_ct"], out_dict["speaker_emb"], counts if counts is not None else n_steps, noise,
                                       factors=out_dict.get("cond_factors"), seeds=seeds)
         out_put = [None] * 12
         out_put[0] = sample
         out_put[10] = kw["src_lens"]
         out_put[11] = out_dict["mel_lens"]
+        if inv is not None:      # back to the caller's order
+            out_put[0] = sample[torch.as_tensor(inv, device=sample.device)].contiguous()
+            out_put[10], out_put[11] = _take_rows(out_put[10], inv, B), _take_rows(out_put[11], inv, B)
         return out_put
 
 
@@ -2333,6 +2479,9 @@ def synthesize_sharded(model: CMTotalTTS, texts, src_lens, spker_embeds=None, sp
     target_frames / segments: duration targets by GLOBAL utterance ([B] / [B, G] and [B, L]; DurationPitchSpeakerNet.forward): each
     rank fits the rows of its own slice, and the fitted lengths are what the ranks agree the plan on."""
     from . import shard
+    if not isinstance(n_steps, (int, np.integer)):
+        raise NotImplementedError("synthesize_sharded: per-utterance step counts are not supported on the sharded path (one int; "
+                                  "CMTotalTTSSynthesize.synthesize and synthesize_stream take a sequence)")
     if buckets is None:
         buckets = shard.FRAME_BUCKETS
     texts = torch.as_tensor(texts)

@@ -356,6 +356,43 @@ int cmtts_retake(cmtts_model* m, const float* mel_known, const uint8_t* regen, c
                  const int64_t* seeds, int B, int T, const int32_t* windows, int N, int Tw, int n_steps,
                  const float* sigmas_host, const float* renoise_std_host, float* mel_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- mixed step counts in one batch: a sampler schedule per utterance (the definition in numpy: cmtts_amd/steps.py).
+ * Utterance b takes n_steps[b] >= 1 evaluations with its own sigmas / renoise_std; its result is, by definition, row b of
+ * cmtts_sample_seeded / cmtts_sample_factored_t run on that schedule (the reference's loop, karras_diffusion.py:801-811, 830-854, on one
+ * row): nothing is new mathematically and the draw numbering stays — draw 0 is x_T, draw 1 + i the re-noise after evaluation i.
+ * ORDER: n_steps must be NON-INCREASING in b (cmtts_amd/steps.py: order gives the stable permutation).  Evaluation i then runs on the
+ * prefix [0, B_i), B_i = #{b : n_steps[b] > i}, of the batch-major workspace: finished utterances leave — a T = 1 draft batched with T = 4
+ * finals costs one evaluation, not four.  An utterance's last evaluation writes its rows straight into `mel`; every row of mel is written
+ * exactly once.  The conditioner branch, the factors and the seeded noise (all max_steps draws of all rows) are set up once for the batch.
+ * Exactly one of `seeds` (DEVICE int64 [B]: cmtts_sample_seeded's noise) and `noise` (device fp32 [n_noise,B,1,T,n_mels], tensor 0 = x_T's
+ * draw, tensor 1 + i the re-noise of evaluation i: max_steps + 1 tensors when a last evaluation re-noises, as cmtts_schedule's do for
+ * n > 1, max_steps otherwise) is given.  cond_p1 .. p_idx: the factors of cmtts_sample_factored_t, or NULL / 0.
+ * The scalings of every (i, b) are computed on the host by cmtts_sample's fp32 expressions and uploaded once, in one table, before the
+ * first launch; a pageable plan is read before the call returns.
+ * Step embedding: while all utterances of an evaluation share the timestep (the reference's own schedules: every sigma is sigma_max) the
+ * call takes cmtts_sample's path, cached row included; otherwise it computes the embedding per row.  Either way the embedding MLP runs on
+ * all B rows of the CALL, never on the shrinking prefix, so its K-slicing (16 slices while 4 * ceil(B / 8) < 128, i.e. B <= 248, else 4)
+ * is that of the uniform call on the same batch: the results are the bits of the uniform entry points on the same full batch at every B, and
+ * do not depend on the batch size among batches of B <= 248.
+ * A plan whose n_steps are all equal and whose columns are all the same IS cmtts_sample_seeded / cmtts_sample_factored_t: same launches,
+ * same bits.  With model option "batch_invariant" an utterance's bits do not depend on which evaluations took the persistent stack.
+ * Validated on the host before anything is launched (CMTTS_E_INVALID, mel untouched): null pointers, both or neither of seeds and noise,
+ * B / T / max_steps < 1, n_steps increasing or outside [1, max_steps], n_steps[0] != max_steps, a negative renoise_std before an
+ * utterance's last evaluation, a non-finite or non-positive sigma where one is read, no speaker_emb for a multi-speaker model.  A short
+ * workspace: CMTTS_E_WORKSPACE.  "batch_invariant" with the F(2,3) stack: CMTTS_E_UNSUPPORTED, as everywhere.
+ * ws: cmtts_sample_mixed_workspace_bytes(m, B, T, max_steps) bytes (0 for a null model or B / T / max_steps < 1): the seeded sampler's
+ * workspace + 24 bytes per (evaluation, utterance). */
+typedef struct cmtts_step_plan {
+    int32_t max_steps;          /* evaluations of the call = n_steps[0] */
+    const int32_t* n_steps;     /* HOST [B], 1 <= n_steps[b] <= max_steps, NON-INCREASING in b */
+    const float* sigmas;        /* HOST [max_steps][B]; (i, b) read only where i < n_steps[b] */
+    const float* renoise_std;   /* HOST [max_steps][B]; < 0 = no re-noise, allowed only at i = n_steps[b] - 1 */
+} cmtts_step_plan;
+size_t cmtts_sample_mixed_workspace_bytes(const cmtts_model* m, int B, int T, int max_steps);
+int cmtts_sample_mixed(cmtts_model* m, const int64_t* seeds, const float* noise, const float* cond_ct, const float* speaker_emb,
+                       int B, int T, const cmtts_step_plan* plan, float* mel, void* ws, size_t ws_bytes, void* stream,
+                       const float* cond_p1, const float* cond_p1t, int p1_ld, int L, const int64_t* mel2ph, const int64_t* p_idx);
+
 /* ---- the same sampler for a RAGGED shard (BASELINE.json configs[3]: variable-length utterances dealt into static frame buckets;
  * new work — the reference synthesizes one padded batch at a time, synthesize.py:195-227).  Every group is one padded (B, T) batch
  * with its own noise / conditioning / output / workspace (cmtts_denoiser_workspace_bytes(m, B, T)) exactly as cmtts_sample takes
