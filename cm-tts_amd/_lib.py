@@ -116,6 +116,13 @@ SIGNATURES = {
     "cmtts_loudness_workspace_bytes": (_i64, [_i, _i64, _i]),
     "cmtts_loudness_measure": (_i, [_vp, _i, _i64, _vp, _i, _vp, _f, _vp, _vp, _sz, _vp]),
     "cmtts_resample_encode_gain": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _f, _vp, _i64, _vp, _vp]),
+    "cmtts_spkenc_create": (_i, [C.POINTER(_vp)]),
+    "cmtts_spkenc_set_tensor": (_i, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i]),
+    "cmtts_spkenc_finalize": (_i, [_vp]),
+    "cmtts_spkenc_destroy": (None, [_vp]),
+    "cmtts_spkenc_workspace_bytes": (_sz, [_i, _i64, _i]),
+    "cmtts_spkenc_features": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "cmtts_spkenc_forward": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
     "cmtts_profile_begin": (_i, [_i, _i]),
     "cmtts_set_fused_resblock": (_i, [_i]),
     "cmtts_set_persistent_denoiser": (_i, [_i]),
@@ -368,6 +375,54 @@ def internal_pack_weights(layout, kmajor, mode=0):
     if _pack_weights(layout.encode(), w.ctypes.data, taps, K, M, int(mode), out.ctypes.data, out.nbytes, C.byref(need)) != 0:
         return None
     return out
+
+
+_spk_hooks = None
+
+
+def _spk():
+    global _spk_hooks
+    load()
+    if _spk_hooks is None:
+        lib = C.CDLL(LIB_PATH)
+        pack, conv, fbank = lib.cmtts_internal_spkenc_pack, lib.cmtts_internal_spkenc_conv, lib.cmtts_internal_spkenc_fbank
+        pack.restype, pack.argtypes = _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, C.POINTER(_sz)]
+        conv.restype, conv.argtypes = _i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]
+        fbank.restype, fbank.argtypes = _i, [_vp, _i, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp]
+        _spk_hooks = (pack, conv, fbank)
+    return _spk_hooks
+
+
+def internal_spkenc_pack(kernel, bias=None, bn=None):
+    """csrc/internal_hooks.h: cmtts_internal_spkenc_pack — the speaker encoder's Conv2D packer with its BatchNorm fold on a Keras kernel
+    (kh, kw, cin, cout), bias [cout] or None, bn [4, cout] (gamma, beta, moving mean, moving variance) or None (tests only; host memory, no
+    GPU).  Returns (fragment stream, folded bias) as float32 arrays."""
+    import numpy as np
+    pack = _spk()[0]
+    k = np.ascontiguousarray(kernel, np.float32)
+    kh, kw, cin, cout = k.shape
+    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    n = None if bn is None else np.ascontiguousarray(bn, np.float32)
+    need = _sz(0)
+    if pack(k.ctypes.data, kh * kw, cin, cout, None, None, None, 0, None, C.byref(need)) != 0:
+        raise ValueError("cmtts_internal_spkenc_pack: shape not covered")
+    frag, bout = np.empty(need.value, np.float32), np.empty(cout, np.float32)
+    rc = pack(k.ctypes.data, kh * kw, cin, cout, None if b is None else b.ctypes.data, None if n is None else n.ctypes.data, frag.ctypes.data,
+              frag.size, bout.ctypes.data, C.byref(need))
+    if rc != 0:
+        raise ValueError("cmtts_internal_spkenc_pack failed")
+    return frag, bout
+
+
+def internal_spkenc_conv(x, frag, bias, res, B, H, W, cin, cout, ks, stride, y, stream):
+    """csrc/internal_hooks.h: cmtts_internal_spkenc_conv — the speaker encoder's Conv2D kernel alone on the caller's device buffers (tests and
+    tools only; pointers as integers, c_void_p or None).  Returns the status."""
+    return _spk()[1](x, frag, bias, res, int(B), int(H), int(W), int(cin), int(cout), int(ks), int(stride), y, stream)
+
+
+def internal_spkenc_fbank(wav, rows, ld, fs, win_length, mode, offsets, max_windows, windows, info, stream):
+    """csrc/internal_hooks.h: cmtts_internal_spkenc_fbank — the fbank kernel alone on kept spans the caller wrote into info (tests only)."""
+    return _spk()[2](wav, int(rows), int(ld), int(fs), int(win_length), int(mode), offsets, int(max_windows), windows, info, stream)
 
 
 def backend():

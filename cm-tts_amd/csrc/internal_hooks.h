@@ -59,6 +59,18 @@ int cmtts_internal_retake_step(const float* x0, const float* known, const uint8_
 // Test hook: the utterance-evaluations (sum over evaluations of the utterances they ran on) launched by the last sampler call of the process:
 // B * n_steps after a uniform call, sum(n_steps[b]) after cmtts_sample_mixed — finished utterances really left, seen without timing anything.
 long cmtts_internal_sample_rows(void);
+// Test hook: the speaker encoder's Conv2D packer with its BatchNorm fold (weight_pack.h: pack_conv2d_bn) on HOST memory.  kernel (taps, cin, cout) floats, bias [cout] or
+// NULL, bn [4][cout] (gamma, beta, moving mean, moving variance) or NULL.  *need = floats of the fragment stream; frag == NULL only queries it.
+int cmtts_internal_spkenc_pack(const float* kernel, int taps, int cin, int cout, const float* bias, const float* bn, float* frag, size_t frag_floats,
+                               float* bias_out, size_t* need);
+// Test hook: conv2d_mfma_kernel alone (speaker_encoder.hip) on the caller's device buffers: x [B][H][W][cin] -> y [B][ceil(H/stride)][ceil(W/stride)][cout] =
+// clip(conv + bias) (+ res, clip again, when res is not NULL), TensorFlow 'same' padding; frag / bias from cmtts_internal_spkenc_pack.
+int cmtts_internal_spkenc_conv(const float* x, const float* frag, const float* bias, const float* res, int B, int H, int W, int cin, int cout, int ks,
+                               int stride, float* y, void* stream);
+// Test hook: the fbank kernel alone on rows whose kept span the CALLER sets: info [rows][4] int32 with (first, last) filled in (device); otherwise as
+// cmtts_spkenc_features behind its trim.  twiddles are made and released inside the call (it synchronises the stream).
+int cmtts_internal_spkenc_fbank(const float* wav, int rows, int64_t ld, int fs, int win_length, int mode, const int32_t* offsets, int max_windows,
+                                float* windows, int32_t* info, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,7 @@
 // and the Winograd weight transforms are each written once below, and a packer is its kernel's loop nest over them.
 #include "weight_pack.h"
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
@@ -243,6 +244,54 @@ std::vector<unsigned short> to_fragment16_split(const std::vector<float>& p, int
     return f;
 }
 
+// The speaker encoder's Conv2D (speaker_encoder.hip: conv2d_mfma_kernel) contracts over k = tap * K + input channel in chunks of 16: A fragments of
+// v_mfma_f32_16x16x4_f32 as [ceil(taps K / 16) chunks][M/16 m-tiles][64 lanes][4]: element j at lane l is k = 16 chunk + 4 (l >> 4) + j, output row 16 mt + (l & 15)
+// — MFMA j of a chunk sums k = 16 chunk + 4 kk + j over its four lane groups kk, so that a lane's four elements are one 16-byte load on the activation side too
+// (four consecutive channels of one pixel).  k beyond taps K is zero.  The row's scale enters in double, one rounding.
+std::vector<float> to_conv2d_fragments(const std::vector<float>& p, int taps, int K, int M, const double* scale) {
+    if (taps < 1 || K < 1 || M < 16 || M % 16) return {};
+    const int ktot = taps * K, nchunk = (ktot + 15) / 16;
+    std::vector<float> f((size_t)nchunk * M * 16);
+    float* o = f.data();
+    for (int c = 0; c < nchunk; ++c)
+        for (int mt = 0; mt < M / 16; ++mt)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int j = 0; j < 4; ++j) {
+                    const int k = 16 * c + 4 * (lane >> 4) + j, row = 16 * mt + (lane & 15);
+                    const double w = k < ktot ? (double)p[(size_t)k * M + row] : 0.0;
+                    *o++ = (float)(scale ? w * scale[row] : w);
+                }
+    return f;
+}
+
+std::vector<float> pack_conv2d_bn(const std::vector<float>& p, int taps, int K, int M, const float* bias, const float* bn, std::vector<float>* bias_out) {
+    std::vector<double> s((size_t)M, 1.0);
+    bias_out->assign((size_t)M, 0.0f);
+    for (int r = 0; r < M; ++r) {
+        double b = bias ? (double)bias[r] : 0.0;
+        if (bn) {
+            s[r] = (double)bn[r] / sqrt((double)bn[3 * (size_t)M + r] + 1e-3);
+            b = (b - (double)bn[2 * (size_t)M + r]) * s[r] + (double)bn[(size_t)M + r];
+        }
+        (*bias_out)[r] = (float)b;
+    }
+    return to_conv2d_fragments(p, taps, K, M, s.data());
+}
+
+// internal_hooks.h: the speaker encoder's packer with its BatchNorm fold, host memory only
+extern "C" int cmtts_internal_spkenc_pack(const float* kernel, int taps, int cin, int cout, const float* bias, const float* bn, float* frag,
+                                          size_t frag_floats, float* bias_out, size_t* need) {
+    if (!kernel || !need || taps < 1 || cin < 1 || cout < 16 || cout % 16) return CMTTS_E_INVALID;
+    *need = (size_t)((taps * cin + 15) / 16) * cout * 16;
+    if (!frag) return 0;
+    if (frag_floats < *need || !bias_out) return CMTTS_E_INVALID;
+    std::vector<float> b;
+    const std::vector<float> f = pack_conv2d_bn(std::vector<float>(kernel, kernel + (size_t)taps * cin * cout), taps, cin, cout, bias, bn, &b);
+    memcpy(frag, f.data(), f.size() * sizeof(float));
+    memcpy(bias_out, b.data(), b.size() * sizeof(float));
+    return 0;
+}
+
 // internal_hooks.h: every packer by name, host memory only
 extern "C" int cmtts_internal_pack_weights(const char* layout, const float* kmajor, int taps, int K, int M, int mode, void* out, size_t out_bytes,
                                            size_t* need) {
@@ -260,6 +309,7 @@ extern "C" int cmtts_internal_pack_weights(const char* layout, const float* kmaj
     else if (name == "wino43_iter_fragments") f = to_wino43_iter_fragments(p, taps, K, M);
     else if (name == "wino43_xres_fragments") f = to_wino43_xres_fragments(p, taps, K, M);
     else if (name == "wino23_xres_fragments") f = to_wino23_xres_fragments(p, taps, K, M);
+    else if (name == "conv2d_fragments") f = to_conv2d_fragments(p, taps, K, M, nullptr);
     else if (name == "fragment16" && m16 && K % 16 == 0 && M % 32 == 0) h = to_fragment16(p, taps, K, M, mode);
     else if (name == "fragment16_iter" && m16 && K % 32 == 0 && M % 32 == 0) h = to_fragment16_iter(p, taps, K, M, mode);
     else if (name == "fragment16_split" && K % 16 == 0 && M % 32 == 0) h = to_fragment16_split(p, taps, K, M);

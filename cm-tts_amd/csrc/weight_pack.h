@@ -24,3 +24,9 @@ std::vector<float> to_wino23_xres_fragments(const std::vector<float>& p, int tap
 std::vector<unsigned short> to_fragment16(const std::vector<float>& p, int taps, int K, int M, int mode);
 std::vector<unsigned short> to_fragment16_iter(const std::vector<float>& p, int taps, int K, int M, int mode);
 std::vector<unsigned short> to_fragment16_split(const std::vector<float>& p, int taps, int K, int M);
+// fp32, v_mfma_f32_16x16x4_f32, the speaker encoder's NHWC Conv2D (speaker_encoder.hip): p = a Keras kernel (kh, kw, cin, cout) = k-major [taps][K][M];
+// taps * K is padded with zeros to a multiple of 16, M % 16 == 0.  scale: one factor per output row applied in double before the rounding, or null.
+std::vector<float> to_conv2d_fragments(const std::vector<float>& p, int taps, int K, int M, const double* scale);
+// The same with the layer's BatchNorm (inference form, epsilon 1e-3) folded in, in double: bn = [4][M] gamma, beta, moving mean, moving variance, or null (no BatchNorm).
+// bias_out [M] = (bias - mean) * s + beta, s = gamma / sqrt(variance + 1e-3).
+std::vector<float> pack_conv2d_bn(const std::vector<float>& p, int taps, int K, int M, const float* bias, const float* bn, std::vector<float>* bias_out);

@@ -33,7 +33,7 @@ def _stream():
 
 
 def _f32(t, device):
-    return t.to(device=device, dtype=torch.float32).contiguous()
+    return torch.as_tensor(t).to(device=device, dtype=torch.float32).contiguous()       # a tensor on `device` passes through; a numpy array is uploaded
 
 
 def _i64(t, device):
@@ -2315,6 +2315,153 @@ def get_vocoder(config, device, root="."):
     vocoder.eval()
     vocoder.remove_weight_norm()
     return vocoder
+
+
+# ---- speaker embeddings from reference audio (csrc/speaker_encoder.hip; definition: cmtts_amd/speaker.py)
+
+class SpeakerEncoder:
+    """The DeepSpeaker ResCNN on the device (deepspeaker/embedding.py: build_model): cmtts_spkenc_* behind one handle."""
+
+    def __init__(self, weights, device="cuda:0"):
+        from .weights import import_deepspeaker
+        self.device = _norm_device(device) if torch.cuda.is_available() else torch.device(device)
+        self.lib = _lib.load()
+        self._h = C.c_void_p()
+        _lib.check(self.lib.cmtts_spkenc_create(C.byref(self._h)))
+        self._ws = _Workspace()
+        self._ready = False
+        _push_state_dict(self.lib, self.lib.cmtts_spkenc_set_tensor, self._h, import_deepspeaker(weights))
+        if self.device.type == "cuda" and torch.cuda.is_available():
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.cmtts_spkenc_finalize(self._h))
+            self._ready = True
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and C is not None:
+            self.lib.cmtts_spkenc_destroy(h)
+            self._h = None
+
+    def _require(self):
+        if not self._ready:
+            raise RuntimeError("SpeakerEncoder: no GPU — cmtts_amd has no CPU fallback (the weights are loaded, the kernels cannot run)")
+
+
+def get_speaker_encoder(weights, device="cuda:0"):
+    """deepspeaker/embedding.py: build_model — `weights`: a dict of the ResCNN's tensors under their Keras names, an .npz of them, or the
+    reference's .h5 checkpoint (weights.import_deepspeaker)."""
+    return SpeakerEncoder(weights, device)
+
+
+def _speaker_windows_bound(n, sample_rate):
+    """The most windows windows="all" can give a row of n samples."""
+    from . import speaker as sp
+    frame_len, frame_step, _ = sp.frame_geometry(sample_rate, 1024)
+    F = sp.num_frames(n, frame_len, frame_step)
+    return max(1, min(sp.MAX_WINDOWS, len(sp.window_offsets(F, "all"))))
+
+
+def speaker_features(enc: SpeakerEncoder, wavs, lengths=None, sample_rate=22050, win_length=1024, windows="center"):
+    """cmtts_spkenc_features: float audio [B, n] -> (windows fp32 [W, 160, 64] on the device, info int32 [B, 4] on the HOST = (first, last,
+    frames, windows) per row).  Reading info back synchronises the stream."""
+    from . import resample as rs
+    enc._require()
+    if int(sample_rate) != rs.NATIVE_RATE:
+        raise ValueError(f"speaker_embedding: the audio must be at the model's sample rate {rs.NATIVE_RATE} Hz, not {sample_rate}")
+    dev = enc.device
+    if isinstance(wavs, (list, tuple)):
+        rows = [torch.as_tensor(np.asarray(w, np.float32)).reshape(-1) for w in wavs]
+        if lengths is None:
+            lengths = [r.numel() for r in rows]
+        ld = max(1, max(r.numel() for r in rows))
+        wavs = torch.zeros(len(rows), ld, dtype=torch.float32)
+        for i, r in enumerate(rows):
+            wavs[i, :r.numel()] = r
+    wavs = torch.as_tensor(wavs)
+    if wavs.dim() == 1:
+        wavs = wavs[None]
+    if not wavs.dtype.is_floating_point:
+        raise ValueError("speaker_embedding: float audio expected")
+    wavs = _f32(wavs, dev)
+    B, n = wavs.shape
+    lens = _clip_lengths(lengths, B, n)
+    offsets = None
+    if isinstance(windows, str):
+        if windows not in ("center", "all"):
+            raise ValueError(f"windows = {windows!r}: expected 'center', 'all' or integer offsets")
+        mode = 0 if windows == "center" else 1
+    else:
+        mode = 2
+        offs = [int(windows)] * B if np.ndim(windows) == 0 else [int(v) for v in windows]
+        if len(offs) != B or min(offs) < 0:
+            raise ValueError("windows: one non-negative frame offset per row")
+    max_w = max(_speaker_windows_bound(v, sample_rate) for v in lens) if mode == 1 else 1
+    with torch.cuda.device(dev):
+        n_valid = torch.tensor(lens, dtype=torch.int32).to(dev)
+        if mode == 2:
+            offsets = torch.tensor(offs, dtype=torch.int32).to(dev)
+        win = torch.empty(B * max_w, 160, 64, dtype=torch.float32, device=dev)
+        info = torch.empty(B, 4, dtype=torch.int32, device=dev)
+        _lib.check(enc.lib.cmtts_spkenc_features(enc._h, _ptr(wavs), B, n, _ptr(n_valid), int(sample_rate), int(win_length), mode,
+                                                 _ptr(offsets), max_w, _ptr(win), _ptr(info), _stream()))
+        info = info.cpu().numpy()
+    if mode == 2:
+        from . import speaker as sp
+        for b in range(B):
+            if info[b, 2] and offs[b] > max(int(info[b, 2]) - sp.NUM_FRAMES, 0):
+                raise ValueError(f"window offset {offs[b]} of row {b} outside [0, {max(int(info[b, 2]) - sp.NUM_FRAMES, 0)}]")
+    return win[:int(info[:, 3].sum())], info
+
+
+def speaker_forward(enc: SpeakerEncoder, windows, row_map, rows):
+    """cmtts_spkenc_forward: windows fp32 [W, 160, 64] (device), row_map int [W] -> embeddings fp32 [rows, 512] (device)."""
+    enc._require()
+    dev = enc.device
+    windows = _f32(windows, dev)
+    W = int(windows.shape[0])
+    with torch.cuda.device(dev):
+        rm = torch.as_tensor(np.asarray(row_map, np.int32).reshape(-1)).to(dev) if not isinstance(row_map, torch.Tensor) else row_map.to(dev, torch.int32)
+        if rm.numel() != W:
+            raise ValueError("speaker_forward: one row_map entry per window")
+        if W == 0:
+            rm = torch.zeros(1, dtype=torch.int32, device=dev)
+        emb = torch.empty(int(rows), 512, dtype=torch.float32, device=dev)
+        nb = enc.lib.cmtts_spkenc_workspace_bytes(max(W, 1), 1, 1)
+        ws = enc._ws.get("spkenc", nb, dev)
+        _lib.check(enc.lib.cmtts_spkenc_forward(enc._h, _ptr(windows) if W else None, W, _ptr(rm), int(rows), _ptr(emb), _ptr(ws), nb, _stream()))
+    return emb
+
+
+def speaker_embedding(enc: SpeakerEncoder, wavs, lengths=None, sample_rate=22050, win_length=1024, windows="center"):
+    """deepspeaker/embedding.py: predict_embedding for a batch — float audio [B, n] (or a list of 1-D arrays) at the model's sample rate ->
+    a DEVICE tensor [B, 512] of unit-norm DeepSpeaker vectors, accepted unchanged as spker_embeds= by synthesize, synthesize_stream,
+    synthesize_sharded and text_state_records.  windows: "center" (one 160-frame window from the middle of the trimmed utterance; the
+    reference draws its offset at random), "all" (every window at hop 80, embeddings averaged), or integer frame offsets (one, or one per row).
+    A row the trim keeps nothing of — silence, constant magnitude — raises ValueError naming the rows (the reference raises IndexError)."""
+    win, info = speaker_features(enc, wavs, lengths, sample_rate, win_length, windows)
+    bad = [b for b in range(info.shape[0]) if info[b, 2] == 0]
+    if bad:
+        raise ValueError(f"speaker_embedding: nothing left of rows {bad} after the silence trim (silent or constant-magnitude audio)")
+    row_map = np.repeat(np.arange(info.shape[0], dtype=np.int32), info[:, 3])
+    return speaker_forward(enc, win, row_map, info.shape[0])
+
+
+class PreDefinedEmbedder(torch.nn.Module):
+    """model/speaker_embedder.py:11-42 — forward(audio) -> numpy (1, 512).  config: the preprocess YAML dict; the ResCNN's weights come from
+    `weights` (default: the reference's checkpoint path, which needs h5py; see weights.import_deepspeaker)."""
+
+    def __init__(self, config, weights="./deepspeaker/pretrained_models/ResCNN_triplet_training_checkpoint_265.h5", device="cuda:0"):
+        super().__init__()
+        self.sampling_rate = config["preprocessing"]["audio"]["sampling_rate"]
+        self.win_length = config["preprocessing"]["stft"]["win_length"]
+        self.embedder_type = config["preprocessing"]["speaker_embedder"]
+        if self.embedder_type != "DeepSpeaker":
+            raise NotImplementedError(f"speaker embedder {self.embedder_type!r}")
+        self.embedder = get_speaker_encoder(weights, device)
+
+    def forward(self, audio):
+        audio = np.asarray(audio.detach().cpu() if isinstance(audio, torch.Tensor) else audio, np.float32).reshape(1, -1)
+        return speaker_embedding(self.embedder, audio, None, self.sampling_rate, self.win_length).cpu().numpy()
 
 
 # ---- a batch that starts from TEXT, sharded over the ranks of a process group by predicted mel length (shard.two_phase): the text

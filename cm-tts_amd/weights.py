@@ -203,3 +203,64 @@ def fold_weight_norm(sd):
         else:
             out[k] = np.asarray(v, np.float32)
     return out
+
+
+DEEPSPEAKER_BETA = -0.4
+DEEPSPEAKER_GAIN = 1.3          # conv kernel std = gain / sqrt(fan_in): chosen so that both clips of clip(0, 20) are hit in every run of the test windows
+
+
+def synth_deepspeaker_state_dict(seed: int = 0, suffix: str = ""):
+    """State dict of the DeepSpeaker ResCNN (deepspeaker/conv_models.py:50-135) under its Keras weight names — `conv64-s/kernel`,
+    `conv64-s_bn/moving_variance`, `res3_1_branch_2b/kernel`, `affine/bias`, ... — each optionally carrying `suffix` (":0", as
+    the variables of a saved model do).  Kernels are (kh, kw, cin, cout).  The scales keep a share of every stage's activations
+    strictly inside (0, 20) and put some on each clip (tests/test_speaker_cpu.py asserts it)."""
+    from .speaker import layer_names
+    sd = OrderedDict()
+
+    def N(name, shape, std, mean=0.0):
+        sd[name + suffix] = _normal("deepspeaker." + name, seed, shape, std, mean)
+
+    for name, k, _, cin, cout in layer_names():
+        N(name + "/kernel", (k, k, cin, cout), DEEPSPEAKER_GAIN / math.sqrt(k * k * cin))
+        N(name + "/bias", (cout,), 0.1)
+        N(name + "_bn/gamma", (cout,), 0.1, 1.0)
+        N(name + "_bn/beta", (cout,), 0.3, DEEPSPEAKER_BETA)
+        N(name + "_bn/moving_mean", (cout,), 0.1)
+        sd[name + "_bn/moving_variance" + suffix] = (0.5 + _rs("deepspeaker." + name + "_bn/moving_variance", seed).uniform(size=(cout,))).astype(np.float32)
+    N("affine/kernel", (2048, 512), 1.0 / math.sqrt(2048))
+    N("affine/bias", (512,), 0.1)
+    return sd
+
+
+def import_deepspeaker(path_or_dict):
+    """The ResCNN's weights as a flat dict of float32 arrays under their Keras names without the ":0" suffix.  Takes a dict, an
+    .npz file, or a Keras .h5 checkpoint (deepspeaker/pretrained_models/ResCNN_triplet_training_checkpoint_265.h5) — the .h5 leg
+    needs h5py, which is not available where this project is developed: that leg is UNTESTED."""
+    from .speaker import layer_names
+    if isinstance(path_or_dict, dict):
+        raw = dict(path_or_dict)
+    elif str(path_or_dict).endswith(".npz"):
+        raw = dict(np.load(path_or_dict))
+    else:
+        try:
+            import h5py
+        except ImportError as e:
+            raise ImportError("import_deepspeaker: reading a Keras .h5 checkpoint needs h5py; convert it to .npz instead") from e
+        raw = {}
+        with h5py.File(path_or_dict, "r") as f:
+            root = f["model_weights"] if "model_weights" in f else f
+
+            def visit(name, obj):
+                if isinstance(obj, h5py.Dataset):
+                    raw["/".join(name.split("/")[-2:])] = np.asarray(obj)
+            root.visititems(visit)
+    out = OrderedDict()
+    for k, v in raw.items():
+        out[k[:-2] if k.endswith(":0") else k] = np.ascontiguousarray(np.asarray(v, np.float32))
+    want = ["affine/kernel", "affine/bias"]
+    for name, _, _, _, _ in layer_names():
+        want += [name + "/kernel", name + "/bias"] + [name + "_bn/" + p for p in ("gamma", "beta", "moving_mean", "moving_variance")]
+    missing = [n for n in want if n not in out]
+    if missing:
+        raise KeyError(f"import_deepspeaker: {len(missing)} tensors missing, first {missing[0]!r}")
+    return OrderedDict((n, out[n]) for n in want)

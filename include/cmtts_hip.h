@@ -69,6 +69,7 @@ const char* cmtts_version(void);
  * (cmtts_resampler_*, cmtts_resample_encode) and cmtts_vocoder_forward_windows_f32: entry points only, still 8; and the duration
  * targets (cmtts_set_duration_targets, a new struct) with cmtts_phoneme_marks: entry points only, still 8.
  * Likewise the loudness measurement (cmtts_loudness_*) and cmtts_resample_encode_gain: entry points only, still 8.
+ * Likewise the speaker encoder (cmtts_spkenc_*, a new opaque handle): entry points only, still 8.
  * A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
  * against before it passes a struct (cmtts_amd/_lib.py does at load time). */
 #define CMTTS_ABI_VERSION 8
@@ -523,6 +524,38 @@ int cmtts_loudness_measure(const float* wav, int rows, int64_t ld, const int32_t
                            float* stats, void* ws, size_t ws_bytes, void* stream);
 int cmtts_resample_encode_gain(cmtts_resampler* r, const float* wav, int rows, int64_t ld, const int32_t* segments, int N, int encoding,
                                float max_wav_value, void* out, int64_t out_ld, const float* gains, void* stream);
+
+/* ---- speaker embeddings from reference audio (the definition in executable form: cmtts_amd/speaker.py).
+ * The zero-shot path's first step: the 512-d DeepSpeaker vector of a reference clip, on the device.  Entry points only: CMTTS_ABI_VERSION stays 8.
+ * cmtts_spkenc_create / _set_tensor / _finalize / _destroy replace deepspeaker/embedding.py: build_model (DeepSpeakerModel + load_weights,
+ *   deepspeaker/conv_models.py:50-135): tensors under their Keras names ("conv64-s/kernel" (5,5,1,64), "conv64-s_bn/moving_variance",
+ *   "res3_1_branch_2b/kernel" (3,3,256,256), "affine/kernel" (2048,512), "affine/bias"; a ":0" suffix is accepted), kernels (kh, kw, cin, cout).
+ *   finalize folds every BatchNorm (epsilon 1e-3) into its conv in double, packs the MFMA fragment streams and uploads them.
+ * cmtts_spkenc_features replaces deepspeaker/audio_ds.py: read_mfcc (34-44) + mfcc_fbank / normalize_frames (126-137) and batcher.py:
+ *   sample_from_mfcc (23-29): wav fp32 [rows][ld] (device) at sample rate fs, n_valid int32 [rows] (device; clamped to [0, ld]) ->
+ *   info int32 [rows][4] (device) = (first, last, frames, windows) — x[first:last] is what the 95th-percentile trim keeps, (-1, -1, 0, 0) where
+ *   it keeps nothing (silence, constant magnitude, one sample above the threshold: the reference raises there) — and the normalised 64-filter
+ *   fbank windows fp32 [sum of windows][160][64] (device; room for rows * max_windows), rows in order, zero rows behind an utterance's end.
+ *   mode 0: one centred window per row; 1: every window at hop 80 plus one aligned to the end, the first max_windows (<= 64) of them;
+ *   2: one window per row at frame offsets int32 [rows] (device; clamped into the utterance).  max_windows must be 1 for modes 0 and 2.
+ *   8000 <= fs <= 40000 and 512 < win_length <= 1024 (a 1024-point FFT).  Two launches, no allocation, no host synchronisation.
+ * cmtts_spkenc_forward replaces deepspeaker/embedding.py: predict_embedding's model.predict: windows fp32 [W][160][64] (device), row_map int32
+ *   [W] (device): the row each window belongs to (an entry outside [0, rows) leaves its window out) -> emb fp32 [rows][512] (device): per row the
+ *   L2-normalised mean of its windows' unit-norm embeddings, zeros for a row without windows.  A window's embedding does not depend on the
+ *   other windows of the call.  ws: cmtts_spkenc_workspace_bytes(rows, ld, max_windows) bytes cover W <= rows * max_windows (0 for rejected
+ *   arguments).  30 launches on `stream`, no allocation, no host synchronisation.
+ * Null pointers, rows or ld < 1, an unsupported fs / win_length / mode / max_windows, a workspace that is too small, a handle that is not
+ * finalized: CMTTS_E_INVALID, checked before any launch. */
+typedef struct cmtts_spkenc cmtts_spkenc;
+int cmtts_spkenc_create(cmtts_spkenc** out);
+int cmtts_spkenc_set_tensor(cmtts_spkenc* e, const char* name, const float* data, const int64_t* shape, int ndim);
+int cmtts_spkenc_finalize(cmtts_spkenc* e);
+void cmtts_spkenc_destroy(cmtts_spkenc* e);
+size_t cmtts_spkenc_workspace_bytes(int rows, int64_t ld, int max_windows);
+int cmtts_spkenc_features(cmtts_spkenc* e, const float* wav, int rows, int64_t ld, const int32_t* n_valid, int fs, int win_length, int mode,
+                          const int32_t* offsets, int max_windows, float* windows, int32_t* info, void* stream);
+int cmtts_spkenc_forward(cmtts_spkenc* e, const float* windows, int W, const int32_t* row_map, int rows, float* emb, void* ws, size_t ws_bytes,
+                         void* stream);
 
 /* ---- measurement hook (no reference counterpart; the reference's only perf tooling is the
  * wall-clock Timer of p_rtf_cm.py:64-108): HIP events recorded on the launch stream around every
