@@ -1,5 +1,6 @@
 // Arguments of the X-resident stacked GEMM (cond_gemm.hip).
 #pragma once
+#include <stdint.h>
 
 struct CondGemmArgs {
     const float* X;       // [B][K = 256][T]

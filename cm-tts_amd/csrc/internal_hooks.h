@@ -14,6 +14,8 @@
 // C = 64 / 128 stages of that path as ONE fused F(4,3) launch, conv_xlq_pair.hip — 0 the forms it replaces (C = 128: two conv_xlq launches; C = 64: the direct pair kernel), 1 (default)
 // with voc_wino's launch-size rule, 2 always; <= 1e-6 on the waveform between the arms).  The switches are process-wide and unsynchronised.  Exported from libcmtts_hip.so so that ctypes can reach it
 // (cmtts_amd/_lib.py: internal_set).
+// The kernel launchers of resblock_args.h, cond_gemm.h and inproj.h are exported too: tests/test_gpu_denoiser_kernels.py calls them directly (-2 = an
+// argument the launcher's header excludes, nothing launched).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -20,6 +20,9 @@ struct ResArgs {
     const float* u;       // F(4,3) form only (resblock_split_w43.hip): [B][256][T] u already formed (three-launch path), else nullptr
 };
 
+// tests/test_gpu_denoiser_kernels.py calls all five launchers directly.  Each returns 0, -3 (HIP error) or -2 (not served, nothing launched): B <= 0,
+// T <= 0, 256 * T beyond a 32-bit element index, x_out == x_in, a->z missing where it is needed (split, split_out, w43), a->W3f missing (w43), a mode
+// other than 1 or 2 (lp).
 #ifdef __cplusplus
 extern "C" {
 #endif

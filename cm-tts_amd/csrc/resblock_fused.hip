@@ -270,7 +270,8 @@ extern "C" void cmtts_resblock_set_tile(int frames) { g_force_fn = frames; }
 extern "C" int cmtts_launch_resblock(const ResArgs* a_in, void* stream) {
     ResArgs a = *a_in;
     a.dbg = g_dbg;
-    if ((long)C * a.T >= (1L << 31)) return -2;
+    // -2 not served: an empty batch, rows beyond the 32-bit element index, x' written over x (neighbouring tiles read its halo)
+    if (a.B <= 0 || a.T <= 0 || (long)C * a.T >= (1L << 31) || a.x_out == a.x_in) return -2;
     // 64-frame tiles halve the weight bytes per MFMA (the measured wall); 32-frame tiles only when 64-frame
     // tiles could not even give every CU one workgroup
     const long tiles64 = (long)((a.T + 63) / 64) * a.B;

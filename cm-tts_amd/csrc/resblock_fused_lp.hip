@@ -218,9 +218,11 @@ int launch_lp(const ResArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-// mode: 1 = bf16, 2 = fp16 operands.  a->W3f / a->Wof point to the 16-bit fragment-order weights.
+// mode: 1 = bf16, 2 = fp16 operands.  a->W3f / a->Wof point to the 16-bit fragment-order weights.  -2 not served: any other mode, an empty
+// batch, rows beyond the 32-bit element index, x' written over x.
 extern "C" int cmtts_launch_resblock_lp(const ResArgs* a, int mode, void* stream) {
-    if ((long)C * a->T >= (1L << 31)) return -2;
+    if (mode != 1 && mode != 2) return -2;
+    if (a->B <= 0 || a->T <= 0 || (long)C * a->T >= (1L << 31) || a->x_out == a->x_in) return -2;
     ResArgs c = *a;
     c.dbg = nullptr;
     return mode == 1 ? launch_lp<1>(c, (hipStream_t)stream) : launch_lp<2>(c, (hipStream_t)stream);

@@ -206,11 +206,11 @@ __global__ __launch_bounds__(64 * NWS) void resblock_split_out_kernel(const ResA
 }  // namespace
 
 // ResidualBlock.forward as two launches for small batches; needs a->z (scratch [B][256][T]).  0 ok, -2 not served
-// (no scratch / shape), -3 HIP error.  The caller decides WHEN (cmtts_api.hip: few 32-frame tiles).
+// (no scratch / shape / x' written over x), -3 HIP error.  The caller decides WHEN (cmtts_api.hip: few 32-frame tiles).
 extern "C" int cmtts_launch_resblock_split(const ResArgs* ap, void* stream_) {
     const ResArgs& a = *ap;
     hipStream_t stream = (hipStream_t)stream_;
-    if (!a.z || a.B <= 0 || a.T <= 0 || (long)C * a.T >= (1L << 31)) return -2;
+    if (!a.z || a.B <= 0 || a.T <= 0 || (long)C * a.T >= (1L << 31) || a.x_out == a.x_in) return -2;
     const size_t lds = (size_t)C * U_LD * sizeof(float);
     dim3 grid((a.T + FN - 1) / FN, a.B, MS);
     hipLaunchKernelGGL(resblock_split_conv_kernel, grid, dim3(64 * NWS), lds, stream, a);

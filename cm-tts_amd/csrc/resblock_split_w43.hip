@@ -168,11 +168,11 @@ __global__ __launch_bounds__(64 * NWS) void resblock_w43_conv_kernel(const ResAr
 }  // namespace
 
 // ResidualBlock.forward in the F(4,3) form as two launches (this conv kernel, resblock_split.hip's projection kernel); needs a->z (scratch
-// [B][256][T]) and a->W3f = the layer's F(4,3) fragments (to_wino43_fragments).  0 ok, -2 not served (no scratch / shape), -3 HIP error.
+// [B][256][T]) and a->W3f = the layer's F(4,3) fragments (to_wino43_fragments).  0 ok, -2 not served (no scratch / shape / x' written over x), -3 HIP error.
 extern "C" int cmtts_launch_resblock_w43(const ResArgs* ap, void* stream_) {
     const ResArgs& a = *ap;
     hipStream_t stream = (hipStream_t)stream_;
-    if (!a.z || !a.W3f || a.B <= 0 || a.B > 65535 || a.T <= 0 || (long)C * a.T >= (1L << 31)) return -2;
+    if (!a.z || !a.W3f || a.B <= 0 || a.B > 65535 || a.T <= 0 || (long)C * a.T >= (1L << 31) || a.x_out == a.x_in) return -2;
     const size_t lds = (size_t)(C + PAD_ROWS) * U_LD * sizeof(float);     // 70.7 KB: two workgroups per CU
     static bool attr_set = false;
     if (!attr_set) {

@@ -27,7 +27,8 @@ The reference computes in fp32 only, so 16-bit MFMA operands have no reference o
     scheme itself, in rms (x 1.3) and in max (x 1.6: two draws of a 5-sigma extreme), i.e. the implementation adds
     nothing to the scheme's own rounding noise; and the fp32 result stays as close to float64 as the reference's.
     The vocoder's ELEMENT-WISE check is tests/test_gpu_vocoder_kernels.py: every one of its kernels alone against
-    float64 on rounded operands (the denoiser's counterpart is test_precision_one_residual_layer here).
+    float64 on rounded operands; the denoiser's is tests/test_gpu_denoiser_kernels.py (the residual-block, gate, conditioner and
+    input-projection kernels alone at their tile edges; test_precision_one_residual_layer here is one shape through the dispatcher).
 """
 import numpy as np
 import pytest
