@@ -353,6 +353,23 @@ def internal_duration_fit(d_rounded, cum, mel_len, src_lens, seg, target, unmet,
     return _duration_fit(d_rounded, cum, mel_len, src_lens, seg, target, unmet, int(B), int(L), int(n_seg), stream)
 
 
+_eval_scalings = None
+
+
+def internal_eval_scalings(sigma, sigma_min, sigma_data):
+    """csrc/internal_hooks.h: cmtts_internal_eval_scalings — the sampler's fp32 scalings of one evaluation, computed on the host (tests only; no
+    GPU).  Returns a float32 array (c_in, c_out, c_skip, 250 log(sigma))."""
+    global _eval_scalings
+    import numpy as np
+    load()
+    if _eval_scalings is None:
+        _eval_scalings = C.CDLL(LIB_PATH).cmtts_internal_eval_scalings
+        _eval_scalings.restype, _eval_scalings.argtypes = None, [C.c_float, C.c_float, C.c_float, _vp]
+    out = np.empty(4, np.float32)
+    _eval_scalings(float(sigma), float(sigma_min), float(sigma_data), out.ctypes.data)
+    return out
+
+
 _pack_weights = None
 
 

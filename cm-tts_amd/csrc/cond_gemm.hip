@@ -157,7 +157,7 @@ extern "C" int cmtts_launch_cond_gemm(const CondGemmArgs* ap, void* stream_) {
 
 namespace {
 // cp[b][r][t] = (ph > 0 ? P1[b][r][ph - 1] : 0) + P2[r][idx],  ph = mel2ph[b][t], idx = p_idx[b][t]:
-// the conditioner projections of all layers expanded from their phoneme-level and pitch-table factors (cmtts_api.hip: cond_factored).
+// the conditioner projections of all layers expanded from their phoneme-level and pitch-table factors (denoiser_side.hip: cond_factored).
 // HBM-bound on the [B][M][T] write; the factors are L2 / Infinity-Cache resident (consecutive frames read the same or the
 // neighbouring phoneme and a neighbouring pitch bucket).  One thread = one frame, CEX_ROWS rows per workgroup, 8 rows in flight.
 constexpr int CEX_ROWS = 64;

@@ -94,7 +94,7 @@ __device__ __forceinline__ void store_granule(unsigned long long* g, unsigned ta
 // (groups: own buffers, own padded T) fill the chip together, and an utterance may be TRIMMED to its first `active` tiles:
 // frames at and beyond Tc = active * 64 behave exactly like frames beyond T (u = 0 there, no neighbour, nothing stored).  Frames
 // closer than NL to Tc differ from the untrimmed result; the caller keeps Tc far enough beyond the frames it uses
-// (cmtts_api.hip: sample_ragged).  The arithmetic of a computed frame is unchanged: every value is bit-identical to the uniform
+// (denoiser_side.hip: cmtts_sample_ragged).  The arithmetic of a computed frame is unchanged: every value is bit-identical to the uniform
 // launch of its own bucket as long as no trimmed frame lies within its receptive field.
 // FACT (round 4): the conditioner projections are gathered from their factors (persist_args.h) wherever cp would be read.
 // WINO == 2 (round 5, the default): the same conv as Winograd F(4,3) over QUADS of output frames with the points 0, +-1, +-2, inf — six

@@ -26,7 +26,7 @@ extern "C" {
 // Names: cond_gemm, persist_tail, inproj_fused, ffn_xres, ffn_fused, text_xres, attn_fused, pred_xl, pred_head, voc_pair,
 // voc_pair3, voc_pairw, voc_rb16, voc_xl, voc_xl16, voc_upsT, post_v4, cond_gemm16, cond_factored, cond_inkernel, xres_small, pred_xres, cwt_in_phoneme, voc_xl_split, text_xt16,
 // persist_wino, ffn_wino, pred_wino, voc_wino, voc_wino43, voc_wino64, voc_wino64_k, voc_qpair, xres_nt, and (round 6, same bits on / off) attn_qb (attention with the queries split over workgroups),
-// stats_mlp (cwt_stats_layers as one launch), energy_head (energy bucketize + embedding add inside the energy predictor's head launch)   (cmtts_api.hip: cmtts_internal_set; the voc_* switches and post_v4: vocoder.hip; the FFT blocks', predictors' and frame side's switches: text_side.hip).
+// stats_mlp (cwt_stats_layers as one launch), energy_head (energy bucketize + embedding add inside the energy predictor's head launch)   (cmtts_api.hip: cmtts_internal_set; the denoiser's and conditioner's switches: denoiser_side.hip; the voc_* switches and post_v4: vocoder.hip; the FFT blocks', predictors' and frame side's switches: text_side.hip).
 int cmtts_internal_set(const char* name, int value);
 // Test hook: the stacked conditioner projections alone, with the model's current precision mode.  cond_ct [B][hidden][T] -> cp [B][NL * C][T]
 // (device pointers).  Returns a cmtts_status.
@@ -61,6 +61,9 @@ int cmtts_internal_retake_step(const float* x0, const float* known, const uint8_
 // Test hook: the utterance-evaluations (sum over evaluations of the utterances they ran on) launched by the last sampler call of the process:
 // B * n_steps after a uniform call, sum(n_steps[b]) after cmtts_sample_mixed — finished utterances really left, seen without timing anything.
 long cmtts_internal_sample_rows(void);
+// Test hook: the sampler's fp32 scalings of one evaluation (denoiser_side.hip: scalings — get_scalings_for_boundary_condition and the rescaled
+// timestep) on the HOST; never touches the GPU.  out4 = (c_in, c_out, c_skip, 250 log(sigma)).
+void cmtts_internal_eval_scalings(float sigma, float sigma_min, float sigma_data, float* out4);
 // Test hook: the speaker encoder's Conv2D packer with its BatchNorm fold (weight_pack.h: pack_conv2d_bn) on HOST memory.  kernel (taps, cin, cout) floats, bias [cout] or
 // NULL, bn [4][cout] (gamma, beta, moving mean, moving variance) or NULL.  *need = floats of the fragment stream; frag == NULL only queries it.
 int cmtts_internal_spkenc_pack(const float* kernel, int taps, int cin, int cout, const float* bias, const float* bn, float* frag, size_t frag_floats,

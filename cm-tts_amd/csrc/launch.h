@@ -1,6 +1,6 @@
-// What the host-side launch sequences (cmtts_api.hip: denoiser and sampler side; text_side.hip: text and frame side; vocoder.hip: the HiFi-GAN
-// generator) share: the generic conv's argument fill and launch, workspace carving, the library-owned side streams and the switch tables.
-// Like fail() in model.h: declared here, defined once in cmtts_api.hip unless noted; small things are inline.
+// What the host-side launch sequences (denoiser_side.hip: denoiser and sampler side; text_side.hip: text and frame side; vocoder.hip: the HiFi-GAN
+// generator) and the rest of the C ABI (cmtts_api.hip) share: the generic conv's argument fill and launch, workspace carving, the library-owned
+// side streams and the switch tables.  Like fail() in model.h: declared here, defined once in cmtts_api.hip unless noted; small things are inline.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -38,8 +38,9 @@ bool side2_ready(SideStream* ss);         // creates side2 / join2 / done0 / don
 int branch_fork(SideStream* ss);          // work queued on ss->side after this sees everything queued on ss->user so far
 int branch_join(SideStream* ss);          // work queued on ss->user after this sees everything queued on ss->side so far
 
-int persist_blocks();                     // workgroups that are certainly co-resident: the CU count
-// The phoneme-level factor of the conditioner projections, p1 [B][res_layers * res_channels][Lp] = Wc * out1 (the frame side computes it beside its predictors)
+int persist_blocks();                     // workgroups that are certainly co-resident: the CU count (denoiser_side.hip)
+// The phoneme-level factor of the conditioner projections, p1 [B][res_layers * res_channels][Lp] = Wc * out1 (the frame side computes it beside its
+// predictors; denoiser_side.hip)
 int cond_phoneme_factor(cmtts_model* m, const float* out1, int B, int Lp, float* p1, hipStream_t s);
 
 // Host copy of an int32 table that is device or page-locked host memory: a host table is read in place, a device table is read
@@ -51,3 +52,6 @@ struct Knob { const char* name; int* var; int lo, hi; };
 int knob_set(const Knob* tab, size_t n, const char* name, int value, bool* found);
 int vocoder_internal_set(const char* name, int value, bool* found);      // vocoder.hip: the generator's switches, asked first by cmtts_internal_set
 int text_internal_set(const char* name, int value, bool* found);         // text_side.hip: the FFT blocks', predictors' and frame side's switches, asked second
+int denoiser_internal_set(const char* name, int value, bool* found);     // denoiser_side.hip: cond_*, persist_tail, persist_wino, inproj_fused, asked last
+extern int g_split_resblock, g_step_cache;      // denoiser_side.hip: the variables of its two rows of cmtts_set_option (resblock_split, step_cache)
+void denoiser_error_word_ready();         // denoiser_side.hip: allocates the process's pinned error word once (cmtts_finalize; cmtts_poll_error reads it)

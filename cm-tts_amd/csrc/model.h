@@ -1,5 +1,5 @@
 // The model and vocoder handles of the C ABI (include/cmtts_hip.h) and what their weight import (import.hip) and their launch
-// sequences (cmtts_api.hip; the text and frame side's: text_side.hip; the vocoder's: vocoder.hip; what those three share beyond the handles: launch.h) share: host tensors, packed convs, the device allocation list, the per-layer weight structs.
+// sequences (the denoiser and sampler's: denoiser_side.hip; the text and frame side's: text_side.hip; the vocoder's: vocoder.hip; the rest of the C ABI: cmtts_api.hip; what those share beyond the handles: launch.h) share: host tensors, packed convs, the device allocation list, the per-layer weight structs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -113,7 +113,7 @@ size_t cmtts_persist_state_floats(int B, int T);   // PersistArgs.xst / PersistG
 int cmtts_launch_denoiser_persist(const PersistArgs* a, int max_blocks, int force, void* stream);
 // 16-bit operand variant (denoiser_persist_lp.hip): mode 1 = bf16, 2 = fp16; W3f / Wof = 16-bit fragment-order weights.
 int cmtts_launch_denoiser_persist_lp(const PersistArgs* a, int mode, int max_blocks, int force, void* stream);
-// Ragged form: a->n_groups, a->grp[], a->n_wg, a->desc[] filled by the caller (cmtts_api.hip: sample_ragged); the halo granules of every
+// Ragged form: a->n_groups, a->grp[], a->n_wg, a->desc[] filled by the caller (denoiser_side.hip: cmtts_sample_ragged); the halo granules of every
 // group must already be cleared on `stream`.  0 = launched, -2 = not supported, -3 = HIP error.
 int cmtts_launch_denoiser_persist_ragged(const PersistArgs* a, void* stream);
 int cmtts_persist_plan(int B, int T, int NL, int max_blocks, int force);   // resident workgroups of the largest launch (0 = path not taken)

@@ -206,7 +206,7 @@ __global__ __launch_bounds__(64 * NWS) void resblock_split_out_kernel(const ResA
 }  // namespace
 
 // ResidualBlock.forward as two launches for small batches; needs a->z (scratch [B][256][T]).  0 ok, -2 not served
-// (no scratch / shape / x' written over x), -3 HIP error.  The caller decides WHEN (cmtts_api.hip: few 32-frame tiles).
+// (no scratch / shape / x' written over x), -3 HIP error.  The caller decides WHEN (denoiser_side.hip: few 32-frame tiles).
 extern "C" int cmtts_launch_resblock_split(const ResArgs* ap, void* stream_) {
     const ResArgs& a = *ap;
     hipStream_t stream = (hipStream_t)stream_;

@@ -1,5 +1,5 @@
 // Per-layer form of the persistent denoiser stack's Winograd F(4,3) residual block (denoiser_persist.hip, WINO == 2) for SMALL batches.
-// The model option "batch_invariant" (cmtts_api.hip) routes every residual layer that would run in the direct form (resblock_fused.hip,
+// The model option "batch_invariant" (denoiser_side.hip) routes every residual layer that would run in the direct form (resblock_fused.hip,
 // resblock_split.hip, the three-launch path) through this conv kernel + resblock_split.hip's projection kernel, so that an utterance's mel
 // has the same bits whether its batch took the persistent stack (large batches) or the per-layer kernels (small ones).
 //
