@@ -123,6 +123,13 @@ SIGNATURES = {
     "cmtts_spkenc_workspace_bytes": (_sz, [_i, _i64, _i]),
     "cmtts_spkenc_features": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "cmtts_spkenc_forward": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "cmtts_mel_basis": (_i, [_i, _i, _i, C.c_double, C.c_double, _vp]),
+    "cmtts_analysis_create": (_i, [_i, _i, _i, _i, _i, C.c_double, C.c_double, C.POINTER(_vp)]),
+    "cmtts_analysis_destroy": (None, [_vp]),
+    "cmtts_analysis_workspace_bytes": (_sz, [_i, _i]),
+    "cmtts_mel_analysis": (_i, [_vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cmtts_phoneme_energy": (_i, [_vp, _i, _i, _vp, _i, C.c_double, C.c_double, _vp, _vp]),
+    "cmtts_pcm_crossfade": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "cmtts_profile_begin": (_i, [_i, _i]),
     "cmtts_set_fused_resblock": (_i, [_i]),
     "cmtts_set_persistent_denoiser": (_i, [_i]),

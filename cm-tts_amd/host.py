@@ -2446,6 +2446,196 @@ def speaker_embedding(enc: SpeakerEncoder, wavs, lengths=None, sample_rate=22050
     return speaker_forward(enc, win, row_map, info.shape[0])
 
 
+# ---- recorded speech in (csrc/mel_analysis.hip; definition: cmtts_amd/analysis.py)
+
+class Analyzer:
+    """The log-mel / energy analysis on the device (preprocessor/preprocessor.py:44-52: TacotronSTFT): cmtts_analysis_* behind one handle."""
+
+    def __init__(self, preprocess_config=None, device="cuda:0"):
+        from . import analysis as an
+        from . import resample as rs
+        pp = (preprocess_config or {}).get("preprocessing", {})
+        stft, mel = pp.get("stft", {}), pp.get("mel", {})
+        self.sample_rate = int(pp.get("audio", {}).get("sampling_rate", an.SAMPLE_RATE))
+        an.check_geometry(stft.get("filter_length", an.N_FFT), stft.get("hop_length", an.HOP), stft.get("win_length", an.N_FFT),
+                          mel.get("n_mel_channels", an.N_MELS))
+        if self.sample_rate != rs.NATIVE_RATE:
+            raise ValueError(f"get_analyzer: the audio must be at the model's sample rate {rs.NATIVE_RATE} Hz, not {self.sample_rate}")
+        self.fmin = float(mel.get("mel_fmin", an.FMIN) or 0.0)
+        self.fmax = float(mel.get("mel_fmax", an.FMAX) or self.sample_rate / 2.0)
+        self.hop = an.HOP
+        self.device = _norm_device(device) if torch.cuda.is_available() else torch.device(device)
+        self.lib = _lib.load()
+        self._h = C.c_void_p()
+        self._ws = _Workspace()
+        self._ready = False
+        if self.device.type == "cuda" and torch.cuda.is_available():
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.cmtts_analysis_create(self.sample_rate, an.N_FFT, an.HOP, an.N_FFT, an.N_MELS, self.fmin, self.fmax, C.byref(self._h)))
+            self._ready = True
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and C is not None:
+            self.lib.cmtts_analysis_destroy(h)
+            self._h = None
+
+    def _require(self):
+        if not self._ready:
+            raise RuntimeError("Analyzer: no GPU — cmtts_amd has no CPU fallback (analysis.py is the definition the kernels are tested against)")
+
+
+def get_analyzer(preprocess_config=None, device="cuda:0"):
+    """The analysis the model's features were made with (preprocessor/preprocessor.py:44-52): `preprocess_config` is the preprocess YAML dict
+    (default: 22050 Hz, 1024 / 256 / 1024, 80 channels over 0-8000 Hz).  Another STFT geometry or sample rate raises ValueError."""
+    return Analyzer(preprocess_config, device)
+
+
+def _audio_rows(wavs, lengths, what):
+    """float or int16 audio as one [B, n] tensor (host or device) and the host-known lengths."""
+    if isinstance(wavs, (list, tuple)):
+        rows = [torch.as_tensor(np.asarray(w.cpu() if hasattr(w, "cpu") else w)).reshape(-1) for w in wavs]
+        if not rows or any(r.dtype != rows[0].dtype for r in rows):
+            raise ValueError(f"{what}: the rows must share one dtype")
+        if lengths is None:
+            lengths = [r.numel() for r in rows]
+        wavs = torch.zeros(len(rows), max(1, max(r.numel() for r in rows)), dtype=rows[0].dtype)
+        for i, r in enumerate(rows):
+            wavs[i, :r.numel()] = r
+    wavs = torch.as_tensor(wavs)
+    if wavs.dim() == 1:
+        wavs = wavs[None]
+    if wavs.dim() != 2 or not (wavs.dtype == torch.int16 or wavs.dtype.is_floating_point):
+        raise ValueError(f"{what}: float or int16 audio [B, n] expected, not {wavs.dtype} {tuple(wavs.shape)}")
+    B, n = wavs.shape
+    lens = [n] * B if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    if len(lens) != B or any(v < 0 or v > n for v in lens):
+        raise ValueError(f"{what}: one length in [0, {n}] per row")
+    return wavs, lens
+
+
+def mel_from_audio(an: Analyzer, wavs, lengths=None, pad="reference", layout="tc"):
+    """Audio.tools.get_mel_from_wav for a batch (cmtts_mel_analysis, one launch): wavs float in [-1, 1] or int16, [B, n] or a list of 1-D rows at
+    22050 Hz; lengths: samples per row (default: all).  pad="reference": the framing the acoustic model's mels were made with (1 + n // 256
+    frames, n > 512); pad="vocoder": frame f covers samples [256 f, 256 f + 256) (n // 256 frames, n > 384) — the framing for copy synthesis.
+    Returns device tensors {"mel": [B, T, 80] (layout="tc", what retake takes) or [B, 80, T] ("ct", what vocoder_infer takes), "mel_lens":
+    int64 [B], "energy": fp32 [B, T]} with T the longest row's frame count and zeros beyond a row's frames.  A row at or below the minimum
+    length raises ValueError before anything is launched."""
+    from . import analysis as A
+    wavs, lens = _audio_rows(wavs, lengths, "mel_from_audio")
+    if layout not in ("tc", "ct"):
+        raise ValueError(f"layout = {layout!r}: expected 'tc' or 'ct'")
+    short = [b for b, v in enumerate(lens) if A.frame_count(v, pad) == 0]
+    if short:
+        raise ValueError(f"mel_from_audio: rows {short} have {A.min_samples(pad)} samples or fewer: too short for pad={pad!r}")
+    an._require()
+    dev, lib = an.device, an.lib
+    B, n = wavs.shape
+    T = max(A.frame_count(v, pad) for v in lens)
+    i16 = wavs.dtype == torch.int16
+    wavs = wavs.to(dev).contiguous() if i16 else _f32(wavs, dev)
+    with torch.cuda.device(dev):
+        n_valid = torch.tensor(lens, dtype=torch.int32).to(dev)
+        mel = torch.empty((B, T, A.N_MELS) if layout == "tc" else (B, A.N_MELS, T), dtype=torch.float32, device=dev)
+        energy = torch.empty(B, T, dtype=torch.float32, device=dev)
+        frames = torch.empty(B, dtype=torch.int32, device=dev)
+        nb = lib.cmtts_analysis_workspace_bytes(B, T)
+        ws = an._ws.get("analysis", nb, dev)
+        _lib.check(lib.cmtts_mel_analysis(an._h, _ptr(wavs), int(i16), B, n, _ptr(n_valid), 0 if pad == "reference" else 1, T,
+                                          0 if layout == "tc" else 1, _ptr(mel), _ptr(energy), _ptr(frames), _ptr(ws), nb, _stream()))
+    return {"mel": mel, "mel_lens": frames.to(torch.int64), "energy": energy}
+
+
+def energy_targets(an: Analyzer, energy, d_targets, mean, std):
+    """preprocessor/preprocessor.py:296-305 and its normalisation (cmtts_phoneme_energy, one launch): energy [B, T] from mel_from_audio,
+    d_targets int [B, L] (an aligner's durations) -> fp32 [B, L] on the device, accepted unchanged as e_targets= by
+    DurationPitchSpeakerNet.forward.  mean, std: stats.json "energy"[2:4]."""
+    if np.ndim(energy) != 2 or np.ndim(d_targets) != 2 or energy.shape[0] != d_targets.shape[0]:
+        raise ValueError(f"energy_targets: energy {tuple(np.shape(energy))} and d_targets {tuple(np.shape(d_targets))} do not fit [B, T] / [B, L]")
+    if not float(std) > 0.0 or math.isnan(float(mean)):
+        raise ValueError("energy_targets: std must be positive, mean a number")
+    an._require()
+    dev = an.device
+    energy = _f32(energy, dev)
+    d = torch.as_tensor(d_targets).to(device=dev, dtype=torch.int32).contiguous()
+    (B, T), L = energy.shape, d.shape[1]
+    with torch.cuda.device(dev):
+        out = torch.empty(B, L, dtype=torch.float32, device=dev)
+        _lib.check(an.lib.cmtts_phoneme_energy(_ptr(energy), B, T, _ptr(d), L, float(mean), float(std), _ptr(out), _stream()))
+    return out
+
+
+def retake_recording_pcm(mel_new, vocoder, pcm_rec, spans, xfade_frames=1):
+    """A retake joined into a RECORDING: mel_new [B,80,T] (vocoder_infer's layout) is the recording's mel after retake(..., spans), pcm_rec
+    the recording itself (a list of int16 rows, or int16 [B, n]; n <= T * hop).  Spans of one utterance whose fades would touch are merged;
+    per merged span only the frames [lo - X, hi + X), X = xfade_frames, are vocoded (cmtts_vocoder_forward_windows_f32 with margin X, in
+    windows that reach the generator's receptive radius beyond them), crossfaded on the device (cmtts_pcm_crossfade; the definition:
+    analysis.crossfade_splice) and spliced into a copy of the recording.  Returns a list of int16 arrays: the samples of frames [lo, hi) are
+    the vocoded audio, the X frames on either side fade linearly between the recording and it — no fade on a side the utterance's start or
+    end clips — and every other sample has the recording's bits.  retake_pcm is the counterpart for audio that vocoder_infer made."""
+    vocoder._require()
+    lib, dev = vocoder.lib, vocoder.device
+    x = _f32(mel_new, dev)
+    B, M, T = x.shape
+    hop, X = vocoder.h.hop, int(xfade_frames)
+    if X < 0:
+        raise ValueError("retake_recording_pcm: xfade_frames must be >= 0")
+    H = lib.cmtts_vocoder_halo_frames(vocoder._h)
+    if H < 0:
+        _lib.check(H)
+    rec = [np.asarray(w.cpu() if hasattr(w, "cpu") else w) for w in pcm_rec]
+    if len(rec) != B or any(w.dtype != np.int16 or w.ndim != 1 or len(w) > T * hop for w in rec):
+        raise ValueError(f"retake_recording_pcm: pcm_rec must hold {B} int16 rows of at most {T * hop} samples")
+    out = [w.copy() for w in rec]
+    per = {}
+    for b, lo, hi in spans:
+        b, lo, hi = int(b), int(lo), int(hi)
+        if not 0 <= b < B or not (0 <= lo < hi <= T and (hi - 1) * hop < len(rec[b])):
+            raise ValueError(f"retake_recording_pcm: span ({b}, {lo}, {hi}) outside the utterances")
+        per.setdefault(b, []).append((lo, hi))
+    cores = []          # [b, lo, hi]: the spans of one utterance merged where their fades touch
+    for b in sorted(per):
+        for lo, hi in sorted(per[b]):
+            if cores and cores[-1][0] == b and lo - X <= cores[-1][2] + X:
+                cores[-1][2] = max(cores[-1][2], hi)
+            else:
+                cores.append([b, lo, hi])
+    if not cores:
+        return out
+    core = max(hi - lo for _, lo, hi in cores)
+    Tw = core + 2 * X + 2 * H
+    if Tw >= T:
+        Tw = T
+    row = (core + 2 * X) * hop
+    wins, tab = [], []
+    rec_rows = np.zeros((len(cores), row), np.int16)
+    for i, (b, lo, hi) in enumerate(cores):
+        start = min(max(lo - X - H, 0), T - Tw)
+        wins.append((b, start, lo - start, hi - lo))
+        lead, trail, n = min(X, lo), min(X, T - hi), len(rec[b])
+        tab.append((lead, hi - lo, trail, (1 if X > 0 and lo - X >= 0 else 0) | (2 if X > 0 and (hi + X) * hop <= n else 0)))
+        s0, s1 = (lo - lead) * hop, min((hi + trail) * hop, n)
+        rec_rows[i, :s1 - s0] = rec[b][s0:s1]
+    N = len(wins)
+    with torch.cuda.device(dev):
+        wtab = torch.tensor(wins, dtype=torch.int32).pin_memory()      # read in place by the call: kept until the copy below has synchronised
+        ftab = torch.tensor(tab, dtype=torch.int32).to(dev)
+        rrows = torch.from_numpy(rec_rows).to(dev)
+        wav_rows = torch.empty(N, row, dtype=torch.float32, device=dev)
+        pcm = torch.empty(N, row, dtype=torch.int16, device=dev)
+        nb = lib.cmtts_vocoder_windows_workspace_bytes(vocoder._h, N, Tw)
+        ws = vocoder._ws.get("voc_stream", nb, dev)
+        _lib.check(lib.cmtts_vocoder_forward_windows_f32(vocoder._h, _ptr(x), B, T, _ptr(wtab), N, Tw, core, X, _ptr(wav_rows), _ptr(ws), nb, _stream()))
+        _lib.check(lib.cmtts_pcm_crossfade(_ptr(wav_rows), _ptr(rrows), _ptr(ftab), N, core, X, hop, _ptr(pcm), _stream()))
+        arr = pcm.cpu().numpy()
+    check_async_error()
+    for i, (b, lo, hi) in enumerate(cores):
+        lead, trail = tab[i][0], tab[i][2]
+        s0, s1 = (lo - lead) * hop, min((hi + trail) * hop, len(rec[b]))
+        out[b][s0:s1] = arr[i, :s1 - s0]
+    return out
+
+
 class PreDefinedEmbedder(torch.nn.Module):
     """model/speaker_embedder.py:11-42 — forward(audio) -> numpy (1, 512).  config: the preprocess YAML dict; the ResCNN's weights come from
     `weights` (default: the reference's checkpoint path, which needs h5py; see weights.import_deepspeaker)."""

@@ -70,6 +70,7 @@ const char* cmtts_version(void);
  * targets (cmtts_set_duration_targets, a new struct) with cmtts_phoneme_marks: entry points only, still 8.
  * Likewise the loudness measurement (cmtts_loudness_*) and cmtts_resample_encode_gain: entry points only, still 8.
  * Likewise the speaker encoder (cmtts_spkenc_*, a new opaque handle): entry points only, still 8.
+ * Likewise the recorded-speech analysis (cmtts_mel_basis, cmtts_analysis_*, cmtts_mel_analysis, cmtts_phoneme_energy, cmtts_pcm_crossfade): still 8.
  * A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
  * against before it passes a struct (cmtts_amd/_lib.py does at load time). */
 #define CMTTS_ABI_VERSION 8
@@ -556,6 +557,53 @@ int cmtts_spkenc_features(cmtts_spkenc* e, const float* wav, int rows, int64_t l
                           const int32_t* offsets, int max_windows, float* windows, int32_t* info, void* stream);
 int cmtts_spkenc_forward(cmtts_spkenc* e, const float* windows, int W, const int32_t* row_map, int rows, float* emb, void* ws, size_t ws_bytes,
                          void* stream);
+
+/* ---- recorded speech in (the definition in executable form: cmtts_amd/analysis.py).
+ * The features the model was trained on, from a waveform, per request and on the device.  Entry points only: CMTTS_ABI_VERSION stays 8.
+ * cmtts_mel_basis replaces the librosa filterbank TacotronSTFT builds (preprocessor/preprocessor.py:44-52: Audio.stft.TacotronSTFT): pure
+ *   host, never touches the GPU: out fp32 [n_mels][n_fft / 2 + 1], the Slaney filterbank (linear below 1000 Hz at 200 / 3 Hz per mel, logarithmic
+ *   above with step ln(6.4) / 27; n_mels + 2 corners equally spaced in mel between fmin and fmax; triangles on linspace(0, fs / 2, bins), each
+ *   scaled by 2 / (f[i+2] - f[i])), computed in double, stored as float.
+ * cmtts_analysis_create / _destroy: an opaque handle that holds the sparse filterbank, the periodic Hann window and the FFT twiddles on the current
+ *   device.  The one STFT geometry every reference config uses — filter_length = win_length = 1024, hop_length = 256, 80 mel channels — with
+ *   8000 <= fs <= 48000 and 0 <= fmin < fmax <= fs / 2 (they shape the filterbank only); anything else is CMTTS_E_INVALID, refused before the GPU
+ *   is touched.
+ * cmtts_mel_analysis replaces preprocessor/preprocessor.py:292, Audio.tools.get_mel_from_wav: wav [rows][ld] (device), fp32 in [-1, 1] (clipped to
+ *   that range) or, with is_int16 != 0, int16 taken as x / 32768; n_valid int32 [rows] (device; clamped to [0, ld]).  pad_mode
+ *   CMTTS_PAD_REFERENCE: 512 reflected samples on either side, 1 + n / 256 frames for n > 512 — what the acoustic model's mels were made with;
+ *   CMTTS_PAD_VOCODER: 384 reflected samples on either side and no centring, n / 256 frames for n > 384, frame f covering samples [256 f, 256 f +
+ *   256), the cell the generator emits for it.  A row at or below the minimum has no frames.  Periodic Hann window, 1024-point real DFT,
+ *   magnitude sqrt(re^2 + im^2) (no + 1e-9 under the root, in either mode) -> energy fp32 [rows][T] = sqrt(sum of mag^2) per frame, mel =
+ *   log(max(basis mag, 1e-5)) as fp32 [rows][T][80] (CMTTS_MEL_TC: what cmtts_retake takes) or [rows][80][T] (CMTTS_MEL_CT: what
+ *   cmtts_vocoder_forward takes; the two hold the same bits), frames int32 [rows] = min(the row's frames, T).  At and beyond a row's frames mel
+ *   and energy are zero (utils/tools.py: pad_2D / pad_1D).  A frame's bits depend on its samples alone: not on the row, the batch or T.  One
+ *   launch on `stream`, no allocation, no host synchronisation.  ws: cmtts_analysis_workspace_bytes(rows, T) bytes (0 for rejected arguments).
+ * cmtts_phoneme_energy replaces preprocessor/preprocessor.py:296-305 (phoneme-level average) and 426-437 (normalize): energy fp32 [B][T],
+ *   durations int32 [B][L] (device; a negative entry counts as 0) -> out fp32 [B][L] (device): (m - mean) / std with m the mean of the phoneme's
+ *   frames [sum d[:l], sum d[:l] + d[l]) — frames ascending, accumulated in double; frames at or beyond T count as zero — and m = 0 for d[l] = 0;
+ *   mean, std: stats.json "energy"[2:4], std > 0.  One launch.
+ * cmtts_pcm_crossfade (no reference counterpart) joins vocoded windows into a recording: wav_rows fp32 [N][(core + 2 xfade_frames) * hop] as
+ *   cmtts_vocoder_forward_windows_f32 wrote them with margin_frames = xfade_frames, rec_rows int16 of the same shape: the recording's samples at
+ *   the same positions; table int32 [N][4] (device) = (lead: margin frames the row holds before the core, core frames, trail: margin frames after
+ *   it, fades: bit 0 the lead, bit 1 the trail) -> out_rows int16 [N][same].  Core samples: wav * 32768 rounded to nearest, saturated.  A faded
+ *   margin (its bit set and all xfade_frames present): rec + w (wav * 32768 - rec), w = (i + 0.5) / (xfade_frames * hop) for the i-th sample from
+ *   the fade's outer end, rounded and saturated alike.  Every other sample: rec's bits.  One launch.
+ * Null pointers, counts < 1 or rows, B, N > 65535, ld >= 2^30, T > 2^22, an unknown pad_mode or layout: CMTTS_E_INVALID, checked before any
+ * launch; a workspace that is too small: CMTTS_E_WORKSPACE. */
+#define CMTTS_PAD_REFERENCE 0
+#define CMTTS_PAD_VOCODER 1
+#define CMTTS_MEL_TC 0
+#define CMTTS_MEL_CT 1
+typedef struct cmtts_analysis cmtts_analysis;
+int cmtts_mel_basis(int fs, int n_fft, int n_mels, double fmin, double fmax, float* out);
+int cmtts_analysis_create(int fs, int filter_length, int hop_length, int win_length, int n_mels, double fmin, double fmax, cmtts_analysis** out);
+void cmtts_analysis_destroy(cmtts_analysis* a);
+size_t cmtts_analysis_workspace_bytes(int rows, int T);
+int cmtts_mel_analysis(cmtts_analysis* a, const void* wav, int is_int16, int rows, int64_t ld, const int32_t* n_valid, int pad_mode, int T, int layout,
+                       float* mel, float* energy, int32_t* frames, void* ws, size_t ws_bytes, void* stream);
+int cmtts_phoneme_energy(const float* energy, int B, int T, const int32_t* durations, int L, double mean, double std, float* out, void* stream);
+int cmtts_pcm_crossfade(const float* wav_rows, const int16_t* rec_rows, const int32_t* table, int N, int core, int xfade_frames, int hop,
+                        int16_t* out_rows, void* stream);
 
 /* ---- measurement hook (no reference counterpart; the reference's only perf tooling is the
  * wall-clock Timer of p_rtf_cm.py:64-108): HIP events recorded on the launch stream around every
