@@ -19,9 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "attention.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "mfma_lane.h"
 
 // No floating-point contraction in this file: attention_kernel and attention_qb_kernel must round s * scale - max the same way.  Left to the
 // compiler (-ffp-contract=fast-honor-pragmas, HIP's default) the first fused it into one fma where product and difference share a basic block,
@@ -34,8 +32,6 @@ namespace {
 constexpr int DH = 128;          // head dimension (hidden 256 / 2 heads)
 constexpr int KB = 64;           // keys per staged chunk
 constexpr int VLD = KB + 1;      // row stride of the V tile [DH][KB]: lanes walk down the channels
-
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 template <int NMT>               // 32-key tiles = waves (query blocks): L in (32 (NMT-1), 32 NMT]
 __global__ __launch_bounds__(64 * NMT) void attention_kernel(const AttnArgs a) {

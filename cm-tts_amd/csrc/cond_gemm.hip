@@ -9,9 +9,7 @@
 // (tests/test_gpu_parity.py::test_cond_gemm_bitwise).
 #include <hip/hip_runtime.h>
 #include "cond_gemm.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "mfma_lane.h"
 
 namespace {
 
@@ -23,11 +21,6 @@ constexpr int NT = FN / 32;
 constexpr int X_LD = FN + 4;
 constexpr int RING = 4;
 constexpr int NG = K / 8;       // k-groups of 8 channels
-
-__device__ __forceinline__ float ldg(const float* base, unsigned idx) {
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (size_t)(idx * 4u));
-}
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 __global__ __launch_bounds__(64 * NW, 2) void cond_gemm_kernel(const CondGemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) float xs[];     // [K][X_LD]

@@ -10,11 +10,7 @@
 #include <hip/hip_runtime.h>
 #include "cond_gemm.h"
 #include "cvt16.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "mfma_lane.h"
 
 namespace {
 
@@ -28,15 +24,6 @@ constexpr int G = K / 16;       // MFMA k-groups
 // k-groups (of MT fragments per operand set) in the ring per wave: a divisor of G, so that a group keeps its slot from pass to pass
 template <int MODE> constexpr int ring_of() { return MODE == 3 ? 4 : 8; }
 static_assert(G % 8 == 0 && G % 4 == 0, "ring slots carry over from one pass to the next");
-
-template <int MODE>
-__device__ __forceinline__ f32x16 mma16(const u32x4& a, const u32x4& b, const f32x16& c) {
-    if (MODE == 1)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // MODE 3 ("fp16x3", fp32-class): two images (hi, lo) of x^T, the lo fragment set behind the hi set, three fp16 MFMAs per product, small terms first
 template <int MODE>

@@ -1,15 +1,13 @@
-// The K loop of the 16-bit HiFi-GAN kernels (resblock_pair16.hip, conv_xl16.hip): fragment types, the 16-bit MFMA, the hand-issued
-// weight ring (conv_loop16) and its two-m-tile variant.  Included by both translation units; everything lives in an anonymous namespace.
+// The K loop of the 16-bit HiFi-GAN kernels (resblock_pair16.hip, conv_xl16.hip): the hand-issued weight ring (conv_loop16) and its
+// two-m-tile variant; fragment types, the 16-bit MFMA and acc_row come from mfma_lane.h.
+// Included by both translation units; everything lives in an anonymous namespace.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "resblock_pair.h"
 #include "cvt16.h"
+#include "mfma_lane.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -24,16 +22,6 @@ constexpr int R1MAX = 25;
 #ifndef CL16_PAD
 #define CL16_PAD 4
 #endif
-
-template <int MODE>
-__device__ __forceinline__ f32x16 mma16(const u32x4& a, const u32x4& b, const f32x16& c) {
-    if (MODE == 1)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 template <int LO, int N, int SEG, class F>
 __device__ __forceinline__ void seg_loop(F& body) {

@@ -19,11 +19,9 @@
 #include "conv_args.h"
 #include "conv_epilogue.h"
 #include "cvt16.h"
+#include "mfma_lane.h"
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // Activations stream through once per launch while every workgroup re-reads the same few hundred KB of weights: the
 // streams are marked non-temporal so that they do not push the weights out of the 4-MB L2 of an XCD (CONV16_NT=0: plain)
@@ -42,14 +40,6 @@ namespace {
 
 constexpr int KC = 32;     // input channels per LDS stage (2 MFMA k-groups)
 constexpr int RSX = 36;    // 16-bit elements per LDS row (72 B)
-
-template <int MODE>
-__device__ __forceinline__ f32x16 mma16(const u32x4& a, const u32x4& b, const f32x16& c) {
-    if (MODE == 1)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 // IO: 0 = fp32 in / fp32 out, 1 = fp32 in / 16-bit activated out (conv1 of a ResBlock pair), 2 = 16-bit activated in /
 // fp32 out (conv2): the intermediate xt of a pair crosses HBM in 16 bits, with exactly the value conv2's staging would

@@ -11,10 +11,7 @@
 #include "conv_args.h"
 #include "conv_epilogue.h"
 #include "cvt16.h"
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#include "mfma_lane.h"
 
 namespace {
 
@@ -23,14 +20,6 @@ constexpr int RS = KC + 8;      // image row in 16-bit elements: a multiple of 1
 constexpr int BN = 96, NT = 3;  // columns per workgroup
 constexpr int RING = 8;
 constexpr int G = KC / 16;
-
-template <int MODE>
-__device__ __forceinline__ f32x16 mma16(const u32x4& a, const u32x4& b, const f32x16& c) {
-    if (MODE == 1)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 template <int LO, int N, int SEG, class F>
 __device__ __forceinline__ void seg_loop(F& body) {

@@ -30,14 +30,12 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "gate.h"
+#include "mfma_lane.h"
 #include "persist_args.h"
 #include "persist_tail.h"
 #include "wino43.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) unsigned long long gu64;
 
 #ifndef WINO_ABL
 #define WINO_ABL 0
@@ -72,22 +70,7 @@ static_assert(((FN + 2) * 2 * 4 + NW * 64 * 4 + NW * 4) % 16 == 0, "row vectors 
 constexpr unsigned SPIN_LIMIT = 1u << 20;     // bounded wait for a neighbour (~2 s); then the timeout word is set and
                                               // this wave stops waiting for the rest of the launch (results invalid)
 
-// An opaque copy of a lane-dependent value: address arithmetic derived from it cannot be hoisted out of the layer
-// loop (hoisted per-lane offsets of the staging / epilogue sections would push the resident tile into scratch).
-__device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-
-// base[idx] with the byte offset formed in 32 bits, so the load takes the (SGPR base + 32-bit VGPR offset) form instead of
-// a 64-bit VGPR address per element (64 of those in flight would not fit the register file).  idx < 2^30.
-__device__ __forceinline__ float ldg(const float* base, unsigned idx) {
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (size_t)(idx * 4u));
-}
-
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-
-__device__ __forceinline__ void store_granule(unsigned long long* g, unsigned tag, float v) {
-    __hip_atomic_store((gu64*)g, ((unsigned long long)tag << 32) | __float_as_uint(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
+// opaque, ldg, acc_row and store_granule: mfma_lane.h
 
 // DBG: cycle stamps of the middle layer (tools/persist_timing.py); the production instance has none.
 // RAGGED (round 3, BASELINE.json configs[3]): a 1-D grid over a tile-descriptor list — the utterances of SEVERAL frame buckets

@@ -15,15 +15,11 @@
 #include <hip/hip_runtime.h>
 #include "cvt16.h"
 #include "gate.h"
+#include "mfma_lane.h"
 #include "persist_args.h"
 #include "persist_tail.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(1))) unsigned long long gu64;
 
 namespace {
 
@@ -36,22 +32,7 @@ constexpr int NT = FN / 32;
 constexpr int RS = 260;         // 16-bit elements per LDS row (520 B)
 constexpr unsigned SPIN_LIMIT = 1u << 20;
 
-__device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-__device__ __forceinline__ float ldg(const float* base, unsigned idx) {
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (size_t)(idx * 4u));
-}
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-__device__ __forceinline__ void store_granule(unsigned long long* g, unsigned tag, float v) {
-    __hip_atomic_store((gu64*)g, ((unsigned long long)tag << 32) | __float_as_uint(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
-template <int MODE>
-__device__ __forceinline__ f32x16 mma16(const u32x4& a, const u32x4& b, const f32x16& c) {
-    if (MODE == 1)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
+// opaque, ldg, acc_row, store_granule and mma16<MODE>: mfma_lane.h
 
 // fp32 pair -> one dword of two 16-bit values in the hi image (and, MODE 3, the fp16 remainders in the lo image IMG
 // elements further on)

@@ -10,9 +10,7 @@
 // generic kernel on mel_prep's output => the same bits (tests/test_gpu_parity.py::test_fused_input_projection_bitwise).
 #include <hip/hip_runtime.h>
 #include "inproj.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "mfma_lane.h"
 
 namespace {
 
@@ -21,8 +19,6 @@ constexpr int C = 256;           // residual channels
 constexpr int FN = 64;           // frames per workgroup
 constexpr int X_LD = FN + 1;
 constexpr int KG = M / 8;        // 10 k-groups
-
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 __global__ __launch_bounds__(256) void inproj_kernel(const InProjArgs a) {
     __shared__ float xs[M * X_LD];

@@ -6,19 +6,12 @@
 // kernel of denoiser_persist4.hip); u_lds / z_lds are two [256][PT_LD] fp32 LDS buffers that no wave reads any more.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "mfma_lane.h"
 #include "persist_args.h"
 
 namespace persist_tail {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int PT_C = 256, PT_NT = 2, PT_LD = 68, PT_RING = 6;
-
-__device__ __forceinline__ int pt_opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-__device__ __forceinline__ float pt_ldg(const float* base, unsigned idx) {
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (size_t)(idx * 4u));
-}
-__device__ __forceinline__ int pt_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 // xold / noise / out: the utterance batch's [B][T][n_mels] tensors (a.xold / a.noise / a.out, or a ragged group's); Tc: frames at and
 // beyond Tc are not stored (Tc = T unless the utterance is trimmed)
@@ -40,9 +33,6 @@ __device__ __forceinline__ void run(const PersistArgs& a, float* u_lds, float* z
 #pragma unroll
         for (int i = 0; i < 4; ++i) row_w[i] = pr[i];
     }
-    auto opaque = [](int v) { return pt_opaque(v); };
-    auto acc_row = [](int r, int ln) { return pt_row(r, ln); };
-    auto ldg = [](const float* p, unsigned i) { return pt_ldg(p, i); };
     // ---- skip head in-kernel: sum(skips)/sqrt(NL) -> skip_projection -> ReLU -> output_projection -> c_out*F + c_skip*x
     // (+ re-noising), the arithmetic of the generic conv epilogues and of mel_post_kernel, in the same order.
     {

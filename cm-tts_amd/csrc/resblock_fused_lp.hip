@@ -13,16 +13,12 @@
 //    global_load_dwordx4 per MFMA, streamed L2 -> VGPR through a 4-deep register ring.
 // At this MFMA rate the kernel is bound by the weight fill (1.05 MB per workgroup) and by the HBM
 // bursts, not by the matrix pipe.
+// What stays fp32 is the fp32 kernels' own source: the gate's bias fetch and the x' / skip epilogue are resblock_direct.h's.
 #include <hip/hip_runtime.h>
 #include "cvt16.h"
-#include "gate.h"
-#include "resblock_args.h"
+#include "resblock_direct.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -32,16 +28,6 @@ constexpr int FN = 64;
 constexpr int NT = FN / 32;
 constexpr int RS = 260;          // 16-bit elements per LDS row (520 B: 8-B aligned rows, bank stride 2 dwords)
 constexpr int RING = 4;
-
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-
-template <int MODE>
-__device__ __forceinline__ f32x16 mma16(const u32x4& a, const u32x4& b, const f32x16& c) {
-    if (MODE == 1)
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 template <int MODE>
 __global__ __launch_bounds__(64 * NW, 4) void resblock_fused_lp_kernel(const ResArgs a) {
@@ -54,7 +40,6 @@ __global__ __launch_bounds__(64 * NW, 4) void resblock_fused_lp_kernel(const Res
     const float* xin = a.x_in + (long)b * C * T;
     const float* cp = a.cp + (long)b * a.cp_bstride;
     const float* dp = a.dp + (long)b * a.vec_stride;
-    const float* dv = a.d + (long)b * a.vec_stride;
 
     // ---- stage u^T[j][m] = cvt(cp + (x + dp)), j = frame - (t0 - 1); lane = frame, waves over channel pairs
     bool ovf = false;
@@ -139,12 +124,7 @@ __global__ __launch_bounds__(64 * NW, 4) void resblock_fused_lp_kernel(const Res
     __syncthreads();   // (2) u dead: its buffer becomes z^T
     {
         float bg[8], bf[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int mg = w * 32 + acc_row(r, lane);
-            bg[r] = a.b3[mg];
-            bf[r] = a.b3[mg + 16];
-        }
+        resdirect::gate_bias(bg, bf, a.b3, w, lane);
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -174,37 +154,7 @@ __global__ __launch_bounds__(64 * NW, 4) void resblock_fused_lp_kernel(const Res
                 for (int j = 0; j < NT; ++j) acc[j] = mma16<MODE>(A[s], Bv[s & 1][j], acc[j]);
             }
         }
-        float* xout = a.x_out + (long)b * C * T;
-        float* skip = a.skip + (long)b * C * T;
-        const bool res_half = w < NW / 2;
-        const float* src = res_half ? xin : skip;
-        float* dst = res_half ? xout : skip;
-        const bool need_src = res_half || a.accum_skip;
-        const int mrow0 = (w % (NW / 2)) * 32;
-        float bo[16], dd[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            bo[r] = a.bo[w * 32 + acc_row(r, lane)];
-            dd[r] = res_half ? dv[mrow0 + acc_row(r, lane)] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int t = t0 + j * 32 + l31;
-            const int t_c = min(t, T - 1);
-            float sv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                sv[r] = need_src ? src[(unsigned)((mrow0 + acc_row(r, lane)) * T + t_c)] : 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int mr = mrow0 + acc_row(r, lane);
-                const float o = acc[j][r] + bo[r];
-                float v;
-                if (res_half) v = (o + (sv[r] + dd[r])) * CMTTS_RSQRT2;
-                else v = a.accum_skip ? o + sv[r] : o;
-                if (t < T) dst[(unsigned)(mr * T + t)] = v;
-            }
-        }
+        resdirect::epilogue(acc, a, b, t0, w, lane);     // fp32, the fp32 kernels' x' / skip expressions
     }
 }
 

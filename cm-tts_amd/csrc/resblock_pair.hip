@@ -28,14 +28,13 @@
 // Accumulation order = the generic kernel's (16-channel chunk, tap, k) and the same epilogue expressions ((acc + b) + x
 // [+ y_old]) => BITWISE equal to the two-launch path (tests/test_gpu_parity.py::test_vocoder_pair_kernel_bitwise).
 #include <hip/hip_runtime.h>
+#include "mfma_lane.h"
 #include "resblock_pair.h"
 #include "xcd_map.h"
 #ifndef XCD_MAP
 #define XCD_MAP 1
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // -DPAIR_DBG=5 (tools/pair_phases.py): every wave stamps the cycle counter at its phase boundaries; results are unchanged
@@ -53,7 +52,6 @@ constexpr int NT = 2;            // n-tiles per wave
 constexpr int RING = 4;          // register ring depth of the weight stream (k-groups of 8 input channels in flight)
 constexpr int R1MAX = 25;        // largest conv1 halo: k = 11, d = 5
 
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 // One conv of the pair on this wave's (m-tile mt) x (n-tiles nq*2, nq*2+1): acc = W * act(src), K loop over

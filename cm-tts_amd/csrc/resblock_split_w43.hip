@@ -17,7 +17,7 @@
 // Per wave 64 k-steps x 12 MFMAs of 32 cycles — the matrix time of one wave of the direct split kernel on a 32-frame tile — for twice the
 // frames: half the waves per utterance at the same per-layer latency.
 #include <hip/hip_runtime.h>
-#include "resblock_args.h"
+#include "resblock_direct.h"
 #include "wino43.h"
 
 using wino43::f32x2;
@@ -42,51 +42,30 @@ __global__ __launch_bounds__(64 * NWS) void resblock_w43_conv_kernel(const ResAr
     const int b = blockIdx.y, t0 = blockIdx.x * FN, T = a.T;
     const int zc = blockIdx.z * NWS + w;           // z channels [16 zc, +16): half zc & 1 of persistent wave zc >> 1
     const int pw = zc >> 1, cb = zc & 1;
-    const float* xin = a.x_in + (long)b * C * T;
-    const float* cp = a.cp + (long)b * a.cp_bstride;
-    const float* dp = a.dp + (long)b * a.vec_stride;
     const float* uin = a.u ? a.u + (long)b * C * T : nullptr;
 
     // ---- stage: lanes = frames, 8 rows in flight per thread; the persistent kernel's expressions (layer 0: u = cp + (x + dp); later
-    // layers form the same value from x' in registers)
-    {
+    // layers form the same value from x' in registers) — resblock_direct.h's staging at 64 frames and 4 waves — or a copy of a->u
+    if (uin) {
         const int t = t0 + lane, t_c = min(t, T - 1);
         constexpr int ROWS_PER_WAVE = C / NWS;       // 64
-        if (uin) {
 #pragma unroll 1
-            for (int i = 0; i < ROWS_PER_WAVE; i += 8) {
-                float uv[8];
+        for (int i = 0; i < ROWS_PER_WAVE; i += 8) {
+            float uv[8];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) uv[q] = uin[(unsigned)((w * ROWS_PER_WAVE + i + q) * T + t_c)];
+            for (int q = 0; q < 8; ++q) uv[q] = uin[(unsigned)((w * ROWS_PER_WAVE + i + q) * T + t_c)];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) u_lds[(w * ROWS_PER_WAVE + i + q) * U_LD + 1 + lane] = t < T ? uv[q] : 0.f;
-            }
-        } else {
-#pragma unroll 1
-            for (int i = 0; i < ROWS_PER_WAVE; i += 8) {
-                float xv[8], cv[8], dq[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int m = w * ROWS_PER_WAVE + i + q;
-                    xv[q] = xin[(unsigned)(m * T + t_c)];
-                    cv[q] = cp[(unsigned)(m * T + t_c)];
-                    dq[q] = dp[m];
-                }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const float uv = cv[q] + (xv[q] + dq[q]);
-                    u_lds[(w * ROWS_PER_WAVE + i + q) * U_LD + 1 + lane] = t < T ? uv : 0.f;
-                }
-            }
+            for (int q = 0; q < 8; ++q) u_lds[(w * ROWS_PER_WAVE + i + q) * U_LD + 1 + lane] = t < T ? uv[q] : 0.f;
         }
         for (int i = tid; i < 2 * C; i += 64 * NWS) {   // halo columns: (side, row)
             const int m = i & (C - 1);
             const bool right = i >= C;
             const int th = right ? t0 + FN : t0 - 1;
             const int thc = min(max(th, 0), T - 1);
-            const float uh = uin ? uin[(unsigned)(m * T + thc)] : cp[(unsigned)(m * T + thc)] + (xin[(unsigned)(m * T + thc)] + dp[m]);
-            u_lds[m * U_LD + (right ? FN + 1 : 0)] = (th >= 0 && th < T) ? uh : 0.f;
+            u_lds[m * U_LD + (right ? FN + 1 : 0)] = (th >= 0 && th < T) ? uin[(unsigned)(m * T + thc)] : 0.f;
         }
+    } else {
+        resdirect::stage_u<FN, NWS>(u_lds, a.x_in + (long)b * C * T, a.cp + (long)b * a.cp_bstride, a.dp + (long)b * a.vec_stride, t0, T, tid);
     }
     __syncthreads();
 
