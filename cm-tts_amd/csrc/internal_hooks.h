@@ -16,6 +16,8 @@
 // (cmtts_amd/_lib.py: internal_set).
 // The kernel launchers of resblock_args.h, cond_gemm.h and inproj.h are exported too: tests/test_gpu_denoiser_kernels.py calls them directly (-2 = an
 // argument the launcher's header excludes, nothing launched).
+// The launch wrappers of kernels.h have one hook each, cmtts_internal_k_<name> (kernel_hooks.hip, declared at the end of this file):
+// tests/test_gpu_frame_kernels.py calls the frame-side and small kernels alone through them (cases: tests/frame_kernel_cases.py).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -76,6 +78,64 @@ int cmtts_internal_spkenc_conv(const float* x, const float* frag, const float* b
 // cmtts_spkenc_features behind its trim.  twiddles are made and released inside the call (it synchronises the stream).
 int cmtts_internal_spkenc_fbank(const float* wav, int rows, int64_t ld, int fs, int win_length, int mode, const int32_t* offsets, int max_windows,
                                 float* windows, int32_t* info, void* stream);
+// Test hooks (kernel_hooks.hip; tests/test_gpu_frame_kernels.py with the cases of tests/frame_kernel_cases.py): the k_* wrappers of kernels.h
+// alone on the caller's device buffers, one hook per wrapper, cmtts_internal_k_<name>(<the wrapper's arguments in its order, defaulted ones
+// included>, stream).  NOTHING is validated: the arguments reach the wrapper unchanged, so the launch is production's (k_dense_small's 16-slice
+// rule, k_conv_post's 16-byte-load rule, k_durations wave against k_durations_serial).  Returns 0; -2 where a bool wrapper (k_ln_linear,
+// k_stats_mlp) declined, nothing launched.  The generic conv needs no hook: cmtts_launch_conv (conv_args.h) is exported.
+// Bitwise contracts these tests hold: k_ln_linear_energy == k_ln_linear + k_energy_embed; k_stats_mlp == three k_dense_small launches;
+// conv_post_v4_kernel == conv_post_kernel; durations wave == serial; a durations table of one value == the scalar form.
+int cmtts_internal_k_embed_tokens(const int64_t* texts, const int64_t* lens, const float* E, const float* omega, const float* tab, int tab_rows,
+                                  float* x, int B, int L, int ld, int C, float scale, void* stream);
+int cmtts_internal_k_layernorm_ct(const float* in, float* out, const float* gamma, const float* beta, float eps, const int64_t* lens, int B, int T,
+                                  int ld, void* stream);
+int cmtts_internal_k_softmax_cols(float* st, const int64_t* lens, int nz, int H, int L, int ld, long zs, void* stream);
+int cmtts_internal_k_pos_embed_add(const float* x, float* out, const float* alpha, const float* omega, const float* tab, int tab_rows, int B, int C,
+                                   int T, int ld, const int64_t* lens, void* stream);
+int cmtts_internal_k_pos_embed_add_lr(const float* src, int ldl, const int64_t* mel2ph, const float* padv, float* out, const float* alpha,
+                                      const float* omega, const float* tab, int tab_rows, int B, int C, int T, void* stream);
+int cmtts_internal_k_chan_linear(const float* x, const float* W, const float* bias, float* out, const int64_t* lens, int B, int C, int T, int ld,
+                                 int O, void* stream);
+int cmtts_internal_k_stats_mlp(const float* in, long in_bs, long in_ks, const float* W0, const float* b0, const float* W1, const float* b1,
+                               const float* W2, const float* b2, float* out, int B, int K0, int N0, int N1, int N2, void* stream);
+int cmtts_internal_k_dense_small(const float* in, long in_bs, long in_ks, const float* Wt, const float* bias, const float* add, float* out, int B,
+                                 int K, int N, int act, void* stream);
+int cmtts_internal_k_energy_embed(const float* x, const float* e_pred, float* e_scaled, const float* e_target, float e_control, const float* bins,
+                                  int nbins, const float* E, float* out1, int64_t* e_idx, int B, int C, int L, int ld, const float* e_table,
+                                  void* stream);
+int cmtts_internal_k_durations(const float* logd, float d_control, float* d_rounded, int* cum, int64_t* mel_len, int B, int L, void* stream);
+int cmtts_internal_k_durations_serial(const float* logd, float d_control, float* d_rounded, int* cum, int64_t* mel_len, int B, int L, void* stream);
+int cmtts_internal_k_durations_table(const float* logd, const float* dtab, float* d_rounded, int* cum, int64_t* mel_len, int B, int L, void* stream);
+int cmtts_internal_k_durations_table_serial(const float* logd, const float* dtab, float* d_rounded, int* cum, int64_t* mel_len, int B, int L,
+                                            void* stream);
+int cmtts_internal_k_pitch_table_scale(float* cwt, const int64_t* mel2ph, const int* cum, const float* ptab, int B, int O, int L, int T, void* stream);
+int cmtts_internal_k_reduce_partials(const float* part, int nseg, const float* bias, const float* res, const int64_t* lens, float* out, int B, int C,
+                                     int L, int ld, void* stream);
+int cmtts_internal_k_ln_linear_energy(const float* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias, float* out,
+                                      const int64_t* ln_lens, const int64_t* out_lens, int B, int T, int ld, const float* xin, const float* e_target,
+                                      float e_control, const float* bins, int nbins, const float* E, float* out1, int64_t* e_idx, float* e_scaled,
+                                      const float* e_table, void* stream);
+int cmtts_internal_k_ln_linear(const float* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias, float* out,
+                               const int64_t* ln_lens, const int64_t* out_lens, int B, int T, int ld, int O, void* stream);
+int cmtts_internal_k_cumsum_durations(const float* dur, int* cum, int64_t* mel_len, int B, int L, void* stream);
+int cmtts_internal_k_mel2ph(const int* cum, int64_t* mel2ph, int B, int L, int T, void* stream);
+int cmtts_internal_k_length_regulate(const float* out1, const int64_t* mel2ph, float* xlr, int B, int C, int ldl, int T, const float* padv,
+                                     void* stream);
+int cmtts_internal_k_pitch_index(const float* cwt, int O, const float* mean_p, const float* std_p, int stat_ld, float std_scale,
+                                 const float* uv_logit, int uv_ld, const uint8_t* uv_mask, float eps, float* r_ws, int64_t* p_idx, float* f0_denorm,
+                                 int B, int T, void* stream);
+int cmtts_internal_k_gather_add(const float* x, const int64_t* idx, const float* E, float* out, int B, int C, int T, void* stream);
+int cmtts_internal_k_lr_gather_add(const float* out1, const int64_t* mel2ph, int ldl, const int64_t* idx, const float* E, float* out, int B, int C,
+                                   int T, void* stream);
+int cmtts_internal_k_mel_prep(const float* x, const float* scale_b, float scale, float* hin, int B, int T, int M, void* stream);
+int cmtts_internal_k_mel_post(const float* F, const float* xold, const float* noise, float c_out, float c_skip, float nstd, float* out, int B, int T,
+                              int M, unsigned* flag, void* stream);
+// rows: device PostRow [B] (persist_args.h: c_out, c_skip, nstd floats, flags uint32)
+int cmtts_internal_k_mel_post_rows(const float* F, const float* xold, const float* noise, const void* rows, float* out, float* out_final, int B,
+                                   int T, int M, unsigned* flag, void* stream);
+int cmtts_internal_k_diff_embed(const float* t, const float* omega, float* emb, int B, int C, void* stream);
+int cmtts_internal_k_conv_post(const float* x, const float* w, const float* bias, float pre_div, float slope, float* wav, int B, int C, int T, int ld,
+                               int KW, void* stream);
 #ifdef __cplusplus
 }
 #endif

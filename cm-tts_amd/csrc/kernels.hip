@@ -387,8 +387,8 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __res
     const float* p = part + ((long)b * nseg * C + c) * ld + t;
     float v = p[0];
     for (int s = 1; s < nseg; ++s) v += p[(long)s * C * ld];
-    v += bias[c];
-    v += res[((long)b * C + c) * ld + t];
+    if (bias) v += bias[c];
+    if (res) v += res[((long)b * C + c) * ld + t];
     if (lens && (int64_t)t >= lens[b]) v = 0.f;
     out[((long)b * C + c) * ld + t] = v;
 }
