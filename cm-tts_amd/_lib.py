@@ -130,6 +130,10 @@ SIGNATURES = {
     "cmtts_mel_analysis": (_i, [_vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_phoneme_energy": (_i, [_vp, _i, _i, _vp, _i, C.c_double, C.c_double, _vp, _vp]),
     "cmtts_pcm_crossfade": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "cmtts_align_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cmtts_align_cost": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "cmtts_align_dtw": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cmtts_align_durations": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_profile_begin": (_i, [_i, _i]),
     "cmtts_set_fused_resblock": (_i, [_i]),
     "cmtts_set_persistent_denoiser": (_i, [_i]),

@@ -2636,6 +2636,111 @@ def retake_recording_pcm(mel_new, vocoder, pcm_rec, spans, xfade_frames=1):
     return out
 
 
+# ---- alignment of a recording to its phonemes (csrc/align.hip; definition: cmtts_amd/align.py)
+
+_ALIGN_WS = _Workspace()
+_ALIGN_KEEP = {}        # per device: the host tables of the latest call, read by its copies on the stream
+
+
+def _align_lengths(what, lens, B, side):
+    lens = [int(v) for v in (lens.tolist() if hasattr(lens, "tolist") else lens)]
+    if len(lens) != B or any(v < 1 or v > side for v in lens):
+        raise ValueError(f"{what}: one length in [1, {side}] per row expected, not {lens}")
+    return lens
+
+
+def _align_mel(what, mel):
+    from . import align as A
+    shape = tuple(torch.as_tensor(mel).shape) if not hasattr(mel, "shape") else tuple(mel.shape)
+    if len(shape) != 3 or shape[2] != A.N_MELS or shape[0] < 1 or not 1 <= shape[1] <= A.MAX_SIDE:
+        raise ValueError(f"{what} must be [B, T, {A.N_MELS}] with 1 <= T <= {A.MAX_SIDE}, not {shape}")
+    return shape
+
+
+def dtw_align(mel_syn, syn_lens, d_syn, mel_rec, rec_lens, normalise=True, device=None):
+    """Dynamic time warping of a rendering against a recording (cmtts_align_cost, cmtts_align_dtw, cmtts_align_durations; the definition:
+    align.py).  mel_syn [B, Ts, 80]: the model's rendering, syn_lens [B] its frames, d_syn int [B, L] its frames per phoneme (sum = syn_lens);
+    mel_rec [B, Tr, 80]: the recording's log-mel (mel_from_audio), rec_lens [B].  Returns device tensors {"d_targets": int64 [B, L], the
+    recording's frames per phoneme (sum = rec_lens; accepted unchanged as d_targets= and by energy_targets), "phoneme_cost": fp32 [B, L], the
+    mean match cost of a phoneme's frames (0 for none), "row": int32 [B, Tr], the rendering frame each recording frame was matched to,
+    "cost": fp32 [B], the path's total over its number of points}.  Lengths and shapes that do not fit, more than 4096 frames a side or
+    durations that do not sum to syn_lens raise ValueError before a device is asked for."""
+    B, Ts, _ = _align_mel("dtw_align: mel_syn", mel_syn)
+    Br, Tr, _ = _align_mel("dtw_align: mel_rec", mel_rec)
+    if Br != B:
+        raise ValueError(f"dtw_align: {B} renderings and {Br} recordings")
+    xl = _align_lengths("dtw_align: syn_lens", syn_lens, B, Ts)
+    yl = _align_lengths("dtw_align: rec_lens", rec_lens, B, Tr)
+    d_host = np.asarray(d_syn.cpu() if hasattr(d_syn, "cpu") else d_syn)
+    if d_host.ndim != 2 or d_host.shape[0] != B or d_host.shape[1] < 1 or not np.array_equal(d_host, np.rint(d_host)):
+        raise ValueError(f"dtw_align: d_syn must hold integers [B, L], not {d_host.dtype} {d_host.shape}")
+    d_host = np.ascontiguousarray(d_host.astype(np.int32))
+    if (d_host < 0).any() or d_host.sum(axis=1).tolist() != xl:
+        raise ValueError(f"dtw_align: d_syn must be non-negative and sum to syn_lens {xl}, not {d_host.sum(axis=1).tolist()}")
+    L = d_host.shape[1]
+    if device is None:
+        device = next((t.device for t in (mel_syn, mel_rec) if isinstance(t, torch.Tensor) and t.is_cuda), "cuda:0")
+    if not torch.cuda.is_available():
+        raise RuntimeError("dtw_align: no GPU — cmtts_amd has no CPU fallback (align.py is the definition the kernels are tested against)")
+    dev, lib = _norm_device(device), _lib.load()
+    x, y = _f32(mel_syn, dev), _f32(mel_rec, dev)
+    xl_h, yl_h = np.asarray(xl, np.int32), np.asarray(yl, np.int32)
+    _ALIGN_KEEP[dev] = (xl_h, yl_h, d_host)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    with torch.cuda.device(dev):
+        d_dev = torch.from_numpy(d_host).to(dev)
+        cost = torch.empty(B, Ts, Tr, dtype=torch.float32, device=dev)
+        row = torch.zeros(B, Tr, dtype=torch.int32, device=dev)
+        total = torch.empty(B, dtype=torch.float32, device=dev)
+        n = torch.empty(B, dtype=torch.int32, device=dev)
+        d_rec = torch.empty(B, L, dtype=torch.int32, device=dev)
+        pc = torch.empty(B, L, dtype=torch.float32, device=dev)
+        nb = lib.cmtts_align_workspace_bytes(B, Ts, Tr)
+        ws = _ALIGN_WS.get("align", nb, dev)
+        _lib.check(lib.cmtts_align_cost(_ptr(x), hp(xl_h), Ts, _ptr(y), hp(yl_h), Tr, B, x.shape[2], int(bool(normalise)), _ptr(cost), _ptr(ws), nb,
+                                        _stream()))
+        _lib.check(lib.cmtts_align_dtw(_ptr(cost), hp(xl_h), hp(yl_h), B, Ts, Tr, _ptr(row), _ptr(total), _ptr(n), _ptr(ws), nb, _stream()))
+        _lib.check(lib.cmtts_align_durations(_ptr(row), _ptr(cost), _ptr(d_dev), hp(d_host), hp(xl_h), hp(yl_h), B, Ts, Tr, L, _ptr(d_rec), _ptr(pc),
+                                             _ptr(ws), nb, _stream()))
+        return {"d_targets": d_rec.to(torch.int64), "phoneme_cost": pc, "row": row, "cost": total / n.to(torch.float32)}
+
+
+def align_recording(model: CMTotalTTS, texts, src_lens, mel_rec, rec_lens, spker_embeds=None, speakers=None, n_steps=4, seeds=None):
+    """Forced alignment of a recording to its text without a second model: the text and frame side run with every control at 1, the sampler
+    renders the phonemes in the given voice (sample_with_cond; `seeds` as there — seeded noise makes the call reproducible, without them the
+    noise is drawn from torch's generator), and dtw_align carries the rendering's phoneme boundaries (d_rounded) over to the recording's
+    frames.  mel_rec [B, Tr, 80], rec_lens [B]: mel_from_audio's "mel" and "mel_lens".  Returns dtw_align's dict plus "mel_syn" [B, Ts, 80] and
+    "d_syn" int32 [B, L].  Limits: a phoneme rendered with 0 frames gets 0 frames; silence the text does not name goes to the
+    first or last phoneme.  Shapes that do not fit raise ValueError before a device is asked for."""
+    tshape = tuple(torch.as_tensor(texts).shape)
+    if len(tshape) != 2:
+        raise ValueError("align_recording: texts must be [B, L]")
+    B, Tr, _ = _align_mel("align_recording: mel_rec", mel_rec)
+    if B != tshape[0]:
+        raise ValueError(f"align_recording: {tshape[0]} texts and {B} recordings")
+    _align_lengths("align_recording: rec_lens", rec_lens, B, Tr)
+    _align_lengths("align_recording: src_lens", src_lens, B, tshape[1])
+    if isinstance(n_steps, (list, tuple, np.ndarray, torch.Tensor)) or int(n_steps) < 1:
+        raise ValueError("align_recording: n_steps must be one positive int")
+    from . import align as A
+    model._require()
+    out = model.duration_pitch_energy_net(speakers, texts, src_lens, spker_embeds=spker_embeds)
+    lens = out["mel_lens"].cpu().tolist()
+    T = out["cond_ct"].shape[2]
+    if min(lens) < 1 or T > A.MAX_SIDE:
+        raise ValueError(f"align_recording: the renderings have {lens} frames; each needs 1 .. {A.MAX_SIDE}")
+    if seeds is None:
+        n_noise = 1 if n_steps == 1 else n_steps + 1
+        noise = torch.randn(n_noise, B, 1, T, model.config.n_mels, dtype=torch.float32, device=model.device)
+        mel_syn = sample_with_cond(model, out["cond_ct"], out["speaker_emb"], int(n_steps), noise)
+    else:
+        mel_syn = sample_with_cond(model, out["cond_ct"], out["speaker_emb"], int(n_steps), seeds=seeds)
+    d_syn = out["d_rounded"].to(torch.int32)
+    res = dtw_align(mel_syn, lens, d_syn, mel_rec, rec_lens, device=model.device)
+    res["mel_syn"], res["d_syn"] = mel_syn, d_syn
+    return res
+
+
 class PreDefinedEmbedder(torch.nn.Module):
     """model/speaker_embedder.py:11-42 — forward(audio) -> numpy (1, 512).  config: the preprocess YAML dict; the ResCNN's weights come from
     `weights` (default: the reference's checkpoint path, which needs h5py; see weights.import_deepspeaker)."""

@@ -71,6 +71,7 @@ const char* cmtts_version(void);
  * Likewise the loudness measurement (cmtts_loudness_*) and cmtts_resample_encode_gain: entry points only, still 8.
  * Likewise the speaker encoder (cmtts_spkenc_*, a new opaque handle): entry points only, still 8.
  * Likewise the recorded-speech analysis (cmtts_mel_basis, cmtts_analysis_*, cmtts_mel_analysis, cmtts_phoneme_energy, cmtts_pcm_crossfade): still 8.
+ * Likewise the alignment of a recording to its phonemes (cmtts_align_*): entry points only, still 8.
  * A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
  * against before it passes a struct (cmtts_amd/_lib.py does at load time). */
 #define CMTTS_ABI_VERSION 8
@@ -604,6 +605,39 @@ int cmtts_mel_analysis(cmtts_analysis* a, const void* wav, int is_int16, int row
 int cmtts_phoneme_energy(const float* energy, int B, int T, const int32_t* durations, int L, double mean, double std, float* out, void* stream);
 int cmtts_pcm_crossfade(const float* wav_rows, const int16_t* rec_rows, const int32_t* table, int N, int core, int xfade_frames, int hop,
                         int16_t* out_rows, void* stream);
+
+/* ---- alignment of a recording to its phonemes by dynamic time warping (the definition in executable
+ * form: cmtts_amd/align.py; no reference counterpart: the reference takes its durations from Montreal Forced Aligner TextGrids, preprocessor/
+ * preprocessor.py:268-282, and compares utterances by DTW only in its evaluation code).  Entry points only: CMTTS_ABI_VERSION stays 8.
+ * x fp32 [B][Ts][80] is the model's own rendering of the phonemes (cmtts_sample*), y fp32 [B][Tr][80] the recording's log-mel
+ * (cmtts_mel_analysis, CMTTS_MEL_TC), both on the device.  x_len, y_len: int32 [B] in HOST memory, 1 <= x_len[b] <= Ts, 1 <= y_len[b] <= Tr; each
+ * call checks them and copies them into its workspace on `stream` (a page-locked array stays valid until the stream has passed the call).
+ * cmtts_align_cost: cost fp32 [B][Ts][Tr] (device), c[i][j] = sum_k (x[i][k] - y[j][k])^2 in the difference form; with normalise != 0 each side's
+ *   per-channel mean over its valid frames (in double, fixed order) is removed first.  Cells with i >= x_len[b] or j >= y_len[b] are neither read
+ *   nor written, in x, y and cost alike.  Two launches (one without normalise).
+ * cmtts_align_dtw: ANY fp32 cost [B][Ts][Tr] (device) -> D[0][0] = c[0][0], D[i][j] = c[i][j] + min(D[i-1][j-1], D[i-1][j], D[i][j-1]), every
+ *   operation one fp32 add or compare, both ends fixed, no band, no slope constraint; ties go to the diagonal, then (i-1, j), then (i, j-1): a
+ *   later candidate wins only if strictly smaller (a NaN never wins).  total fp32 [B] = D[x_len-1][y_len-1], path_len int32 [B] = points of the
+ *   path walked back from there (on row 0 it goes left, on column 0 up: at most x_len + y_len - 1 points whatever the matrix holds), row int32
+ *   [B][Tr]: for j < y_len[b] the path's point in column j with the smallest c[i][j], ties to the smallest i; entries at or beyond y_len[b] are
+ *   not written.  The result has the bits of the definition for every matrix.  Two launches: the cost into the DP's order, then one workgroup per pair.
+ * cmtts_align_durations: row as cmtts_align_dtw wrote it (non-decreasing per row; entries are clamped to [0, x_len)), the cost it was made from,
+ *   d_syn int32 [B][L] (device): the rendering's frames per phoneme, a negative entry counts as 0 -> d_rec int32 [B][L]: the recording's frames j
+ *   whose row[j] lies in the phoneme's frames (sum = y_len[b] when sum d_syn = x_len[b]; 0 for a phoneme of 0 frames), phoneme_cost fp32 [B][L]:
+ *   the fp32 sum of c[row[j]][j] over those frames, j ascending, divided by their number; 0 for none.  d_syn_host: the same table in host memory,
+ *   or NULL; when given, a negative entry or sum d_syn[b] != x_len[b] is refused.  One launch.
+ * ws: cmtts_align_workspace_bytes(B, Ts, Tr) bytes, the same for the three calls (0 for B < 1, B > 65535, a side < 1 or > 4096); it holds the
+ *   lengths, the means, the cost in the DP's order and one byte per cell and anti-diagonal step for the walk back (about 5 bytes per cell).
+ * Refused before the GPU is touched (CMTTS_E_INVALID, message in cmtts_last_error): a null pointer, a length outside its side, n_mels != 80,
+ * L outside [1, 65536], d_syn_host that does not sum to x_len; a workspace that is too small: CMTTS_E_WORKSPACE. */
+size_t cmtts_align_workspace_bytes(int B, int Ts, int Tr);
+int cmtts_align_cost(const float* x, const int32_t* x_len, int Ts, const float* y, const int32_t* y_len, int Tr, int B, int n_mels, int normalise,
+                     float* cost, void* ws, size_t ws_bytes, void* stream);
+int cmtts_align_dtw(const float* cost, const int32_t* x_len, const int32_t* y_len, int B, int Ts, int Tr, int32_t* row, float* total,
+                    int32_t* path_len, void* ws, size_t ws_bytes, void* stream);
+int cmtts_align_durations(const int32_t* row, const float* cost, const int32_t* d_syn, const int32_t* d_syn_host, const int32_t* x_len,
+                          const int32_t* y_len, int B, int Ts, int Tr, int L, int32_t* d_rec, float* phoneme_cost, void* ws, size_t ws_bytes,
+                          void* stream);
 
 /* ---- measurement hook (no reference counterpart; the reference's only perf tooling is the
  * wall-clock Timer of p_rtf_cm.py:64-108): HIP events recorded on the launch stream around every
