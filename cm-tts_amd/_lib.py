@@ -134,6 +134,13 @@ SIGNATURES = {
     "cmtts_align_cost": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "cmtts_align_dtw": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_align_durations": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "cmtts_pitch_tables": (_i, [_i, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "cmtts_pitch_create": (_i, [_i, _i, C.c_double, C.c_double, C.POINTER(_vp)]),
+    "cmtts_pitch_destroy": (None, [_vp]),
+    "cmtts_pitch_workspace_bytes": (_sz, [_i, _i]),
+    "cmtts_pitch_nacf": (_i, [_vp, _vp, _i, _i, _i64, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cmtts_pitch_track": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "cmtts_pitch_targets": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_profile_begin": (_i, [_i, _i]),
     "cmtts_set_fused_resblock": (_i, [_i]),
     "cmtts_set_persistent_denoiser": (_i, [_i]),

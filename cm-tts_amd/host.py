@@ -2741,6 +2741,164 @@ def align_recording(model: CMTotalTTS, texts, src_lens, mel_rec, rec_lens, spker
     return res
 
 
+# ---- pitch of a recording (csrc/pitch.hip; definition: cmtts_amd/pitch.py)
+
+class PitchTracker:
+    """F0 tracking and the CWT pitch targets on the device (utils/pitch_tools.py:81-118, preprocessor/preprocessor.py:408-414): cmtts_pitch_*
+    behind one handle."""
+
+    def __init__(self, preprocess_config=None, device="cuda:0"):
+        from . import pitch as P
+        from . import resample as rs
+        pp = (preprocess_config or {}).get("preprocessing", {})
+        pitch = pp.get("pitch", {})
+        if pitch.get("pitch_type", "cwt") != "cwt":
+            raise ValueError(f"get_pitch_tracker: pitch_type {pitch.get('pitch_type')!r}: only 'cwt' targets are made")
+        if pitch.get("pitch_norm", "log") != "log":
+            raise ValueError(f"get_pitch_tracker: pitch_norm {pitch.get('pitch_norm')!r}: only 'log' is supported")
+        self.sample_rate = int(pp.get("audio", {}).get("sampling_rate", P.SAMPLE_RATE))
+        if self.sample_rate != rs.NATIVE_RATE:
+            raise ValueError(f"get_pitch_tracker: the audio must be at the model's sample rate {rs.NATIVE_RATE} Hz, not {self.sample_rate}")
+        self.geometry = P.Geometry(self.sample_rate, int(pp.get("stft", {}).get("hop_length", P.HOP)), P.FLOOR_HZ, P.CEILING_HZ)
+        self.hop, self.lags = self.geometry.hop, self.geometry.LMAX + 2
+        self.device = _norm_device(device) if torch.cuda.is_available() else torch.device(device)
+        self.lib = _lib.load()
+        self._h = C.c_void_p()
+        self._ws = _Workspace()
+        self._ready = False
+        if self.device.type == "cuda" and torch.cuda.is_available():
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.cmtts_pitch_create(self.sample_rate, self.hop, P.FLOOR_HZ, P.CEILING_HZ, C.byref(self._h)))
+            self._ready = True
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and C is not None:
+            self.lib.cmtts_pitch_destroy(h)
+            self._h = None
+
+    def _require(self):
+        if not self._ready:
+            raise RuntimeError("PitchTracker: no GPU — cmtts_amd has no CPU fallback (pitch.py is the definition the kernels are tested against)")
+
+    def _workspace(self, B, T):
+        nb = self.lib.cmtts_pitch_workspace_bytes(B, T)
+        return self._ws.get("pitch", nb, self.device), nb
+
+
+def get_pitch_tracker(preprocess_config=None, device="cuda:0"):
+    """The pitch analysis the model's pitch targets are made with: `preprocess_config` is the preprocess YAML dict (default: 22050 Hz, hop 256,
+    pitch_type "cwt", pitch_norm "log"; floor 80 Hz and ceiling 750 Hz are the reference's constants).  Another pitch_type, pitch_norm or
+    sample rate raises ValueError."""
+    return PitchTracker(preprocess_config, device)
+
+
+def _pitch_frames(pt, lens, what):
+    from . import pitch as P
+    T = max(pt.geometry.frame_count(v) for v in lens)
+    if T > P.MAX_FRAMES:
+        raise ValueError(f"{what}: {T} frames; at most {P.MAX_FRAMES} per row")
+    return T
+
+
+def pitch_nacf(pt: PitchTracker, wavs, lengths=None):
+    """The normalised autocorrelation of every frame (cmtts_pitch_nacf, one launch): wavs float in [-1, 1] or int16, [B, n] or a list of 1-D rows at
+    22050 Hz; lengths: samples per row (default: all).  Returns device tensors {"r": fp32 [B, T, LMAX + 2], "pk": fp32 [B, T], "frames":
+    int32 [B]} with T = 1 + n // 256 of the longest row: frame f is centred on sample 256 f, as mel frame f of mel_from_audio(pad="reference")."""
+    wavs, lens = _audio_rows(wavs, lengths, "pitch_nacf")
+    T = _pitch_frames(pt, lens, "pitch_nacf")
+    pt._require()
+    dev, lib = pt.device, pt.lib
+    B, n = wavs.shape
+    i16 = wavs.dtype == torch.int16
+    wavs = wavs.to(dev).contiguous() if i16 else _f32(wavs, dev)
+    with torch.cuda.device(dev):
+        n_valid = torch.tensor(lens, dtype=torch.int32).to(dev)
+        r = torch.empty(B, T, pt.lags, dtype=torch.float32, device=dev)
+        pk = torch.empty(B, T, dtype=torch.float32, device=dev)
+        frames = torch.empty(B, dtype=torch.int32, device=dev)
+        ws, nb = pt._workspace(B, T)
+        _lib.check(lib.cmtts_pitch_nacf(pt._h, _ptr(wavs), int(i16), B, n, _ptr(n_valid), T, _ptr(r), _ptr(pk), _ptr(frames), _ptr(ws), nb, _stream()))
+    return {"r": r, "pk": pk, "frames": frames}
+
+
+def pitch_track(pt: PitchTracker, r, pk, frames):
+    """The tracker's path on ANY fp32 r [B, T, LMAX + 2], pk [B, T], frames int [B] (cmtts_pitch_track, two launches) -> {"lag": int32 [B, T]
+    (0 = unvoiced), "f0": fp32 [B, T]}: the bits of pitch.track for every input."""
+    shape = tuple(np.shape(r))
+    if len(shape) != 3 or shape[2] != pt.lags or shape[0] < 1 or shape[1] < 1 or tuple(np.shape(pk)) != shape[:2] or tuple(np.shape(frames)) != shape[:1]:
+        raise ValueError(f"pitch_track: r [B, T, {pt.lags}], pk [B, T] and frames [B] expected, not {shape}, {tuple(np.shape(pk))}, {tuple(np.shape(frames))}")
+    from . import pitch as P
+    if shape[1] > P.MAX_FRAMES:
+        raise ValueError(f"pitch_track: at most {P.MAX_FRAMES} frames per row")
+    pt._require()
+    dev, lib = pt.device, pt.lib
+    B, T, _ = shape
+    r, pk = _f32(r, dev), _f32(pk, dev)
+    frames = torch.as_tensor(frames).to(device=dev, dtype=torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        lag = torch.empty(B, T, dtype=torch.int32, device=dev)
+        f0 = torch.empty(B, T, dtype=torch.float32, device=dev)
+        ws, nb = pt._workspace(B, T)
+        _lib.check(lib.cmtts_pitch_track(pt._h, _ptr(r), _ptr(pk), _ptr(frames), B, T, _ptr(lag), _ptr(f0), _ptr(ws), nb, _stream()))
+    return {"lag": lag, "f0": f0}
+
+
+def pitch_from_audio(pt: PitchTracker, wavs, lengths=None):
+    """utils/pitch_tools.py:81-118 for a batch, per request and on the device (pitch_nacf, pitch_track): returns device tensors {"f0": fp32 [B, T]
+    in Hz, 0 where unvoiced, "uv": bool [B, T], "lag": int32 [B, T], "frames": int32 [B]}; zeros (uv False) at and beyond a row's frames."""
+    a = pitch_nacf(pt, wavs, lengths)
+    t = pitch_track(pt, a["r"], a["pk"], a["frames"])
+    T = t["f0"].shape[1]
+    inside = torch.arange(T, device=pt.device)[None, :] < a["frames"][:, None]
+    return {"f0": t["f0"], "uv": (t["f0"] == 0) & inside, "lag": t["lag"], "frames": a["frames"]}
+
+
+def pitch_targets_from_f0(pt: PitchTracker, f0, frames, check=True):
+    """preprocessor/preprocessor.py:408-414 for a batch (cmtts_pitch_targets, one launch), on a contour that came from pitch_from_audio or from
+    elsewhere — a flattened question, a transposed melody: f0 [B, T] in Hz with 0 where unvoiced, frames int [B], 3 <= T <= 4096.  Returns
+    the dict DurationPitchSpeakerNet.forward takes as p_targets= — {"cwt_spec": fp32 [B, T, 10], "f0_mean": fp32 [B], "f0_std": fp32 [B],
+    "uv": bool [B, T]} — plus "f0" and "status" (int32 [B]: 0 fine, 1 no voiced frame, 2 a constant contour, 3 fewer than 3 frames; the
+    reference drops such clips, preprocessor.py:310, 314).  check=True copies the B status ints once and raises ValueError naming the rows
+    whose status is not 0; check=False returns them and synchronises nothing."""
+    shape = tuple(np.shape(f0))
+    from . import pitch as P
+    if len(shape) != 2 or shape[0] < 1 or not 3 <= shape[1] <= P.MAX_FRAMES or tuple(np.shape(frames)) != shape[:1]:
+        raise ValueError(f"pitch_targets_from_f0: f0 [B, T] with 3 <= T <= {P.MAX_FRAMES} and frames [B] expected, not {shape}, {tuple(np.shape(frames))}")
+    pt._require()
+    dev, lib = pt.device, pt.lib
+    B, T = shape
+    f0 = _f32(f0, dev)
+    frames = torch.as_tensor(frames).to(device=dev, dtype=torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        cwt = torch.empty(B, T, P.CWT_SCALES, dtype=torch.float32, device=dev)
+        mean = torch.empty(B, dtype=torch.float32, device=dev)
+        std = torch.empty(B, dtype=torch.float32, device=dev)
+        uv = torch.empty(B, T, dtype=torch.uint8, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        ws, nb = pt._workspace(B, T)
+        _lib.check(lib.cmtts_pitch_targets(pt._h, _ptr(f0), _ptr(frames), B, T, _ptr(cwt), _ptr(mean), _ptr(std), _ptr(uv), _ptr(status), _ptr(ws), nb,
+                                           _stream()))
+    if check:
+        bad = {b: s for b, s in enumerate(status.cpu().tolist()) if s != 0}
+        if bad:
+            why = {1: "no voiced frame", 2: "a constant contour", 3: "fewer than 3 frames"}
+            raise ValueError("pitch_targets: no CWT targets for rows " + ", ".join(f"{b} ({why.get(s, s)})" for b, s in bad.items()))
+    return {"cwt_spec": cwt, "f0_mean": mean, "f0_std": std, "uv": uv.view(torch.bool), "f0": f0, "status": status}
+
+
+def pitch_targets(pt: PitchTracker, wavs, lengths=None, check=True):
+    """The pitch targets of recordings: pitch_from_audio, then pitch_targets_from_f0 (four launches in all).  Rows shorter than 3 frames
+    (512 samples) raise ValueError before a device is asked for."""
+    wavs, lens = _audio_rows(wavs, lengths, "pitch_targets")
+    short = [b for b, v in enumerate(lens) if pt.geometry.frame_count(v) < 3]
+    if short:
+        raise ValueError(f"pitch_targets: rows {short} have fewer than 3 frames ({2 * pt.hop} samples)")
+    _pitch_frames(pt, lens, "pitch_targets")
+    p = pitch_from_audio(pt, wavs, lens)
+    return pitch_targets_from_f0(pt, p["f0"], p["frames"], check=check)
+
+
 class PreDefinedEmbedder(torch.nn.Module):
     """model/speaker_embedder.py:11-42 — forward(audio) -> numpy (1, 512).  config: the preprocess YAML dict; the ResCNN's weights come from
     `weights` (default: the reference's checkpoint path, which needs h5py; see weights.import_deepspeaker)."""

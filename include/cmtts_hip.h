@@ -72,6 +72,7 @@ const char* cmtts_version(void);
  * Likewise the speaker encoder (cmtts_spkenc_*, a new opaque handle): entry points only, still 8.
  * Likewise the recorded-speech analysis (cmtts_mel_basis, cmtts_analysis_*, cmtts_mel_analysis, cmtts_phoneme_energy, cmtts_pcm_crossfade): still 8.
  * Likewise the alignment of a recording to its phonemes (cmtts_align_*): entry points only, still 8.
+ * Likewise the pitch of a recording (cmtts_pitch_*, a new opaque handle): entry points only, still 8.
  * A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
  * against before it passes a struct (cmtts_amd/_lib.py does at load time). */
 #define CMTTS_ABI_VERSION 8
@@ -638,6 +639,52 @@ int cmtts_align_dtw(const float* cost, const int32_t* x_len, const int32_t* y_le
 int cmtts_align_durations(const int32_t* row, const float* cost, const int32_t* d_syn, const int32_t* d_syn_host, const int32_t* x_len,
                           const int32_t* y_len, int B, int Ts, int Tr, int L, int32_t* d_rec, float* phoneme_cost, void* ws, size_t ws_bytes,
                           void* stream);
+
+/* ---- pitch of a recording: F0 tracking and the CWT pitch targets (the definition in executable form:
+ * cmtts_amd/pitch.py).  Entry points only: CMTTS_ABI_VERSION stays 8.  What comes out is what cmtts_set_variance_controls takes as cwt_spec,
+ * f0_mean, f0_std and uv.  The recipes are the public ones (Boersma 1993; Torrence & Compo as pycwt implements them), restated: NOT Praat bit
+ * for bit — frame f is centred on sample hop_length * f, the centre of mel frame f of CMTTS_PAD_REFERENCE (the reference shifts Praat's frames
+ * by a fixed lpad instead), and the peak is refined by a parabola through three lags (no sinc interpolation).
+ * cmtts_pitch_tables: pure host, never touches the GPU: the tables a handle holds, for the CPU tests.  geometry int32 [3] = (W: the window, 3
+ *   periods of the floor rounded up to even; LMIN = ceil(fs / ceiling); LMAX = floor(fs / floor)); the others may be NULL: window fp32 [W] =
+ *   0.5 - 0.5 cos(2 pi (i + 0.5) / W), r_w double [LMAX + 2]: its autocorrelation over r_w[0], lg fp32 [LMAX + 2] = log2(lag) (lg[0] = 0),
+ *   lg_floor = log2(fs / floor), cwt fp32 [10][cwt_n]: the periodised DOG-2 wavelets of transform length cwt_n (a power of two in [4, 4096]).
+ *   All made in double, rounded once.
+ * cmtts_pitch_create / _destroy: an opaque handle that holds these tables, the CWT's for every length 4 .. 4096, on the current device.
+ *   Refused (CMTTS_E_INVALID) before the GPU is touched: fs < 1, hop_length outside [1, 1024], not 0 < floor < ceiling <= fs / 2, W > 2048,
+ *   LMAX + 2 > 512.
+ * cmtts_pitch_nacf replaces the framing and autocorrelation of parselmouth's Sound.to_pitch_ac (utils/pitch_tools.py:102-104): wav [rows][ld]
+ *   (device), fp32 clipped to [-1, 1] or, with is_int16 != 0, int16 taken as x / 32768; n_valid int32 [rows] (device; clamped to [0, ld];
+ *   samples at or beyond it are not read).  Frame f < 1 + n / hop_length covers samples [hop f - W / 2, hop f + W / 2), zeros outside the clip:
+ *   mean removed, pk fp32 [rows][T] = max |x|, Hann window, a[tau] = sum_i x[i] x[i + tau], r fp32 [rows][T][LMAX + 2] = a[tau] / a[0] / r_w[tau]
+ *   (all 0 when a[0] is not positive), frames int32 [rows] = min(the row's frames, T); zeros at and beyond a row's frames.  Fixed summation
+ *   order, no atomics: a frame's bits depend on its samples alone.  One launch.
+ * cmtts_pitch_track replaces the path finder of to_pitch_ac (voicing threshold 0.6, silence threshold 0.03, octave cost 0.01, octave-jump cost
+ *   0.35, voiced / unvoiced cost 0.14, 8 candidates): ANY fp32 r, pk (device), frames int32 [B] (device; clamped to [0, T]) -> lag int32 [B][T]
+ *   (0 = unvoiced), f0 fp32 [B][T] = fs / (lag + the vertex of the parabola through r[lag-1 .. lag+1]), 0 where unvoiced; zeros at and beyond a
+ *   row's frames.  Candidates, strengths, transitions and tie rules as cmtts_amd/pitch.py states them, every operation one rounded fp32
+ *   operation: lag has the bits of the definition for every input, NaN and infinities included.  Two launches.
+ * cmtts_pitch_targets replaces preprocessor/preprocessor.py:408-414 (get_cont_lf0, mean / std, get_lf0_cwt): f0 fp32 [B][T] (device; 0 =
+ *   unvoiced), frames -> uv uint8 [B][T] = (f0 == 0), the continuous contour (ends filled, interior runs interpolated linearly), its log, f0_mean
+ *   and f0_std fp32 [B] (population; in double, fixed order), cwt_spec fp32 [B][T][10] = the real part of the DOG-2 CWT of (lf0 - mean) / std at
+ *   scales 0.01 2^j, dt = 0.005, zero-padded to the next power of two >= the row's frames (4 at the least).  status int32 [B]: 0 fine, 1 no
+ *   voiced frame, 2 a constant contour (std == 0), 3 fewer than 3 frames; for 1-3 cwt_spec is zeros, f0_std 1 and f0_mean the single log value
+ *   (0 for 1 and 3).  A row's result depends on the row alone; zeros at and beyond a row's frames.  One launch.
+ * ws: cmtts_pitch_workspace_bytes(B, T) bytes, the same for the three calls (0 for B < 1, B > 65535, T < 1, T > 4096).  No allocation, no
+ * host synchronisation.  Null pointers, rows or B outside [1, 65535], T outside [1, 4096] ([3, 4096] for the targets), ld >= 2^30:
+ * CMTTS_E_INVALID, checked before any launch; a workspace that is too small: CMTTS_E_WORKSPACE. */
+typedef struct cmtts_pitch cmtts_pitch;
+int cmtts_pitch_tables(int fs, int hop_length, double floor_hz, double ceiling_hz, int32_t* geometry, float* window, double* r_w, float* lg,
+                       float* lg_floor, int cwt_n, float* cwt);
+int cmtts_pitch_create(int fs, int hop_length, double floor_hz, double ceiling_hz, cmtts_pitch** out);
+void cmtts_pitch_destroy(cmtts_pitch* p);
+size_t cmtts_pitch_workspace_bytes(int B, int T);
+int cmtts_pitch_nacf(cmtts_pitch* p, const void* wav, int is_int16, int rows, int64_t ld, const int32_t* n_valid, int T, float* r, float* pk,
+                     int32_t* frames, void* ws, size_t ws_bytes, void* stream);
+int cmtts_pitch_track(cmtts_pitch* p, const float* r, const float* pk, const int32_t* frames, int B, int T, int32_t* lag, float* f0, void* ws,
+                      size_t ws_bytes, void* stream);
+int cmtts_pitch_targets(cmtts_pitch* p, const float* f0, const int32_t* frames, int B, int T, float* cwt_spec, float* f0_mean, float* f0_std,
+                        uint8_t* uv, int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- measurement hook (no reference counterpart; the reference's only perf tooling is the
  * wall-clock Timer of p_rtf_cm.py:64-108): HIP events recorded on the launch stream around every
