@@ -123,6 +123,13 @@ SIGNATURES = {
     "cmtts_spkenc_workspace_bytes": (_sz, [_i, _i64, _i]),
     "cmtts_spkenc_features": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "cmtts_spkenc_forward": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "cmtts_ge2e_create": (_i, [C.POINTER(_vp)]),
+    "cmtts_ge2e_set_tensor": (_i, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i]),
+    "cmtts_ge2e_finalize": (_i, [_vp]),
+    "cmtts_ge2e_destroy": (None, [_vp]),
+    "cmtts_ge2e_workspace_bytes": (_sz, [_i, _i]),
+    "cmtts_ge2e_features": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "cmtts_ge2e_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "cmtts_mel_basis": (_i, [_i, _i, _i, C.c_double, C.c_double, _vp]),
     "cmtts_analysis_create": (_i, [_i, _i, _i, _i, _i, C.c_double, C.c_double, C.POINTER(_vp)]),
     "cmtts_analysis_destroy": (None, [_vp]),
@@ -458,6 +465,64 @@ def internal_spkenc_conv(x, frag, bias, res, B, H, W, cin, cout, ks, stride, y, 
 def internal_spkenc_fbank(wav, rows, ld, fs, win_length, mode, offsets, max_windows, windows, info, stream):
     """csrc/internal_hooks.h: cmtts_internal_spkenc_fbank — the fbank kernel alone on kept spans the caller wrote into info (tests only)."""
     return _spk()[2](wav, int(rows), int(ld), int(fs), int(win_length), int(mode), offsets, int(max_windows), windows, info, stream)
+
+
+_ge2e_hooks = None
+
+
+def _ge2e():
+    global _ge2e_hooks
+    load()
+    if _ge2e_hooks is None:
+        lib = C.CDLL(LIB_PATH)
+        mel, layer, tail = lib.cmtts_internal_ge2e_mel, lib.cmtts_internal_ge2e_layer, lib.cmtts_internal_ge2e_tail
+        basis = lib.cmtts_internal_ge2e_mel_basis
+        mel.restype, mel.argtypes = _i, [_vp, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]
+        layer.restype, layer.argtypes = _i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]
+        tail.restype, tail.argtypes = _i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]
+        basis.restype, basis.argtypes = _i, [_vp]
+        _ge2e_hooks = (mel, layer, tail, basis)
+    return _ge2e_hooks
+
+
+def internal_ge2e_mel(wav, rows, ld, n_valid, mode, max_windows, T, windows, win_lens, info, stream):
+    """csrc/internal_hooks.h: cmtts_internal_ge2e_mel — the GE2E front end alone (tests and tools only; pointers as integers or None)."""
+    return _ge2e()[0](wav, int(rows), int(ld), n_valid, int(mode), int(max_windows), int(T), windows, win_lens, info, stream)
+
+
+def internal_ge2e_layer(x, N, T, K, wih, whh, bias, lens, tile, pre, hseq, hlast, stream):
+    """csrc/internal_hooks.h: cmtts_internal_ge2e_layer — one LSTM layer (projection GEMM + recurrence) on the caller's device buffers."""
+    return _ge2e()[1](x, int(N), int(T), int(K), wih, whh, bias, lens, int(tile), pre, hseq, hlast, stream)
+
+
+def internal_ge2e_tail(hlast, W, lin_t, lin_b, emb_w, row_map, rows, emb, stream):
+    """csrc/internal_hooks.h: cmtts_internal_ge2e_tail — Linear + ReLU + norm per window and the row means on the caller's device buffers."""
+    return _ge2e()[2](hlast, int(W), lin_t, lin_b, emb_w, row_map, int(rows), emb, stream)
+
+
+def internal_ge2e_mel_basis():
+    """csrc/internal_hooks.h: cmtts_internal_ge2e_mel_basis — csrc/mel_basis.cpp at n_fft = 551: float32 [40, 276] (host only)."""
+    import numpy as np
+    out = np.empty((40, 276), np.float32)
+    if _ge2e()[3](out.ctypes.data) != 0:
+        raise ValueError("cmtts_internal_ge2e_mel_basis failed")
+    return out
+
+
+def ge2e_pack_lstm(w, bias_ih=None, bias_hh=None):
+    """The lstm_fragments stream (csrc/weight_pack.h: to_lstm_fragments) of a torch LSTM matrix [1024, K] as a float32 array, and — with the two
+    biases — their sum in packed row order (tests and tools only; host memory)."""
+    import numpy as np
+    from . import ge2e
+    w = np.asarray(w, np.float32)
+    raw = internal_pack_weights("lstm_fragments", np.ascontiguousarray(w.T)[None])
+    if raw is None:
+        raise ValueError("lstm_fragments: shape not covered")
+    frag = raw.view(np.float32)
+    if bias_ih is None:
+        return frag
+    b = (np.asarray(bias_ih, np.float32) + np.asarray(bias_hh, np.float32))[ge2e.packed_row(np.arange(1024))]
+    return frag, np.ascontiguousarray(b, np.float32)
 
 
 def backend():

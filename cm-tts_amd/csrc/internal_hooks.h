@@ -45,7 +45,7 @@ int cmtts_internal_mel_window_gather(const float* mel_ct, int B, int T, const in
 int cmtts_internal_noise_bits(const int64_t* seeds, int B, int T, int M, int first_draw, int n_draws, int64_t t0, uint32_t* bits, void* stream);
 // Test hook: one of the host-side weight packers (weight_pack.h) on HOST memory; never touches the GPU.  layout = the packer's name without "to_"
 // (fragment_order, fragment_iter_order, fragment16, fragment16_iter, fragment16_split, wino_fragments, wino43_fragments, wino_iter_fragments,
-// wino43_iter_fragments, wino43_xres_fragments, wino23_xres_fragments); kmajor [taps][K][M] floats; mode 1 = bf16 / 2 = fp16 for fragment16 and
+// wino43_iter_fragments, wino43_xres_fragments, wino23_xres_fragments, conv2d_fragments, lstm_fragments (taps 1, M 1024)); kmajor [taps][K][M] floats; mode 1 = bf16 / 2 = fp16 for fragment16 and
 // fragment16_iter, ignored elsewhere.  *need = the size of the packed stream in bytes, padding included; out == NULL only queries it.  An unknown
 // layout, a (taps, K, M) the packer does not cover or out_bytes < *need returns CMTTS_E_INVALID.
 int cmtts_internal_pack_weights(const char* layout, const float* kmajor, int taps, int K, int M, int mode, void* out, size_t out_bytes, size_t* need);
@@ -78,6 +78,20 @@ int cmtts_internal_spkenc_conv(const float* x, const float* frag, const float* b
 // cmtts_spkenc_features behind its trim.  twiddles are made and released inside the call (it synchronises the stream).
 int cmtts_internal_spkenc_fbank(const float* wav, int rows, int64_t ld, int fs, int win_length, int mode, const int32_t* offsets, int max_windows,
                                 float* windows, int32_t* info, void* stream);
+// Test hooks of the GE2E encoder (ge2e.h; tests/test_gpu_ge2e.py, tools/ge2e_bench.py).  _mel: the front end alone, as cmtts_ge2e_features without a
+// handle (the tables are made and released inside the call, which synchronises the stream).  _layer (kernel_hooks.hip): one LSTM layer — the projection
+// GEMM and the recurrence — on the caller's device buffers: x [N][T][K], wih / whh the lstm_fragments streams of cmtts_internal_pack_weights, bias
+// [1024] in packed row order, lens int32 [N] or NULL, tile 16 (-2 otherwise), pre [N][T][1024] scratch, hseq [N][T][256], hlast [N][256].  _tail
+// (kernel_hooks.hip): hlast [W][256], lin_t [256 k][256 o] -> emb_w [W][256] and, with row_map (DEVICE int32 [W]) not NULL, emb [rows][256].
+// _mel_basis: mel_basis.cpp at
+// the odd transform length, out [40][276] (host memory, no GPU).
+int cmtts_internal_ge2e_mel(const float* wav, int rows, int64_t ld, const int32_t* n_valid, int mode, int max_windows, int T, float* windows,
+                            int32_t* win_lens, int32_t* info, void* stream);
+int cmtts_internal_ge2e_layer(const float* x, int N, int T, int K, const float* wih, const float* whh, const float* bias, const int32_t* lens, int tile,
+                              float* pre, float* hseq, float* hlast, void* stream);
+int cmtts_internal_ge2e_tail(const float* hlast, int W, const float* lin_t, const float* lin_b, float* emb_w, const int32_t* row_map, int rows,
+                             float* emb, void* stream);
+int cmtts_internal_ge2e_mel_basis(float* out);
 // Test hooks (kernel_hooks.hip; tests/test_gpu_frame_kernels.py with the cases of tests/frame_kernel_cases.py): the k_* wrappers of kernels.h
 // alone on the caller's device buffers, one hook per wrapper, cmtts_internal_k_<name>(<the wrapper's arguments in its order, defaulted ones
 // included>, stream).  NOTHING is validated: the arguments reach the wrapper unchanged, so the launch is production's (k_dense_small's 16-slice

@@ -3,6 +3,7 @@
 // under test is the one production makes, grid choice included — and returns 0 (-2 where a bool wrapper declined).  No product path calls one.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "ge2e.h"
 #include "internal_hooks.h"
 #include "kernels.h"
 #include "persist_args.h"
@@ -146,6 +147,15 @@ int cmtts_internal_k_conv_post(const float* x, const float* w, const float* bias
                                int KW, void* stream) {
     k_conv_post(x, w, bias, pre_div, slope, wav, B, C, T, ld, KW, ST);
     return 0;
+}
+// the GE2E encoder's launches alone (ge2e.h; tests/test_gpu_ge2e.py): the launcher's status is the hook's (-2: an argument no instance covers)
+int cmtts_internal_ge2e_layer(const float* x, int N, int T, int K, const float* wih, const float* whh, const float* bias, const int32_t* lens, int tile,
+                              float* pre, float* hseq, float* hlast, void* stream) {
+    return cmtts_launch_ge2e_layer(x, N, T, K, wih, whh, bias, lens, tile, pre, hseq, hlast, stream);
+}
+int cmtts_internal_ge2e_tail(const float* hlast, int W, const float* lin_t, const float* lin_b, float* emb_w, const int32_t* row_map, int rows,
+                             float* emb, void* stream) {
+    return cmtts_launch_ge2e_tail(hlast, W, lin_t, lin_b, emb_w, row_map, rows, emb, stream);
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@ constexpr int MEL_FPB = 4;                    // consecutive frames per workgrou
 constexpr int MEL_NNZ_MAX = 2 * MEL_BINS;     // a bin lies between two neighbouring corners, so it feeds at most two triangles
 
 // mel_basis.cpp (host only).  out [n_mels][n_fft / 2 + 1]: the Slaney filterbank, computed in double, stored as float.  -1 for arguments
-// outside 2 <= n_fft <= 65536 (even), 1 <= n_mels <= 1024, 0 <= fmin < fmax <= fs / 2, fs >= 1.
+// outside 2 <= n_fft <= 65536 (even or odd: n_fft / 2 + 1 bins on linspace(0, fs / 2, bins); cmtts_mel_basis admits even ones only), 1 <= n_mels <= 1024, 0 <= fmin < fmax <= fs / 2, fs >= 1.
 int mel_basis(int fs, int n_fft, int n_mels, double fmin, double fmax, float* out);
 // The periodic Hann window [1024] and the twiddles exp(-2 pi i k / 1024), k = 0 .. 511, as (cos, sin) pairs [512][2]: made in double,
 // rounded to float once.

@@ -239,7 +239,7 @@ struct cmtts_analysis {
 extern "C" {
 
 int cmtts_mel_basis(int fs, int n_fft, int n_mels, double fmin, double fmax, float* out) {
-    if (mel_basis(fs, n_fft, n_mels, fmin, fmax, out) != 0)
+    if (n_fft % 2 || mel_basis(fs, n_fft, n_mels, fmin, fmax, out) != 0)       // the entry point stays even-only; mel_basis() itself takes the GE2E front end's odd 551
         return fail(CMTTS_E_INVALID, "cmtts_mel_basis: null out, or outside fs >= 1, even 2 <= n_fft <= 65536, 1 <= n_mels <= 1024, 0 <= fmin < fmax <= fs / 2");
     return 0;
 }

@@ -23,7 +23,8 @@ double linspace(double a, double b, int n, int i) { return i == n - 1 ? b : a + 
 }  // namespace
 
 int mel_basis(int fs, int n_fft, int n_mels, double fmin, double fmax, float* out) {
-    if (!out || fs < 1 || n_fft < 2 || n_fft > 65536 || n_fft % 2 || n_mels < 1 || n_mels > 1024) return -1;
+    // an odd n_fft (the GE2E front end's 551, ge2e.hip) has n_fft / 2 + 1 bins on the same linspace(0, fs / 2, bins)
+    if (!out || fs < 1 || n_fft < 2 || n_fft > 65536 || n_mels < 1 || n_mels > 1024) return -1;
     if (!(fmin >= 0.0) || !(fmin < fmax) || !(fmax <= fs / 2.0)) return -1;
     const int bins = n_fft / 2 + 1;
     std::vector<double> f(n_mels + 2);

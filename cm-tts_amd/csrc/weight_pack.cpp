@@ -278,6 +278,27 @@ std::vector<float> pack_conv2d_bn(const std::vector<float>& p, int taps, int K, 
     return to_conv2d_fragments(p, taps, K, M, s.data());
 }
 
+// The GE2E encoder's LSTM matrices (ge2e.hip: W_ih for the projection GEMM, W_hh for the recurrence): p = the PyTorch matrix [4 H gate rows][K] handed
+// over k-major [K][M = 1024], gate rows in torch's order i, f, g, o (row = gate * 256 + unit).  A fragments of v_mfma_f32_16x16x4_f32 as
+// [ceil(K / 16) chunks][64 row tiles][64 lanes][4] like to_conv2d_fragments, over PACKED rows q = 64 (unit / 16) + 16 gate + unit % 16: the row tiles
+// 4 g .. 4 g + 3 are i, f, g, o of hidden units 16 g .. 16 g + 15, so the wave that owns them holds all four gates of a unit in one lane.
+int lstm_packed_row(int q) { return ((q % 64) / 16) * 256 + 16 * (q / 64) + q % 16; }
+
+std::vector<float> to_lstm_fragments(const std::vector<float>& p, int K, int M) {
+    if (K < 1 || M != 1024) return {};
+    const int nchunk = (K + 15) / 16;
+    std::vector<float> f((size_t)nchunk * M * 16);
+    float* o = f.data();
+    for (int c = 0; c < nchunk; ++c)
+        for (int rt = 0; rt < M / 16; ++rt)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int j = 0; j < 4; ++j) {
+                    const int k = 16 * c + 4 * (lane >> 4) + j, row = lstm_packed_row(16 * rt + (lane & 15));
+                    *o++ = k < K ? p[(size_t)k * M + row] : 0.0f;
+                }
+    return f;
+}
+
 // internal_hooks.h: the speaker encoder's packer with its BatchNorm fold, host memory only
 extern "C" int cmtts_internal_spkenc_pack(const float* kernel, int taps, int cin, int cout, const float* bias, const float* bn, float* frag,
                                           size_t frag_floats, float* bias_out, size_t* need) {
@@ -310,6 +331,7 @@ extern "C" int cmtts_internal_pack_weights(const char* layout, const float* kmaj
     else if (name == "wino43_xres_fragments") f = to_wino43_xres_fragments(p, taps, K, M);
     else if (name == "wino23_xres_fragments") f = to_wino23_xres_fragments(p, taps, K, M);
     else if (name == "conv2d_fragments") f = to_conv2d_fragments(p, taps, K, M, nullptr);
+    else if (name == "lstm_fragments" && taps == 1) f = to_lstm_fragments(p, K, M);
     else if (name == "fragment16" && m16 && K % 16 == 0 && M % 32 == 0) h = to_fragment16(p, taps, K, M, mode);
     else if (name == "fragment16_iter" && m16 && K % 32 == 0 && M % 32 == 0) h = to_fragment16_iter(p, taps, K, M, mode);
     else if (name == "fragment16_split" && K % 16 == 0 && M % 32 == 0) h = to_fragment16_split(p, taps, K, M);

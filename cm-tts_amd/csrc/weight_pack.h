@@ -29,4 +29,8 @@ std::vector<unsigned short> to_fragment16_split(const std::vector<float>& p, int
 std::vector<float> to_conv2d_fragments(const std::vector<float>& p, int taps, int K, int M, const double* scale);
 // The same with the layer's BatchNorm (inference form, epsilon 1e-3) folded in, in double: bn = [4][M] gamma, beta, moving mean, moving variance, or null (no BatchNorm).
 // bias_out [M] = (bias - mean) * s + beta, s = gamma / sqrt(variance + 1e-3).
+// fp32, v_mfma_f32_16x16x4_f32, the GE2E encoder's LSTM matrices (ge2e.hip): p = [K][M = 1024] k-major, gate rows in torch's order; the stream is
+// [ceil(K / 16)][64 row tiles][64 lanes][4] over packed rows q (lstm_packed_row(q) = the torch row q holds): row tiles 4 g .. 4 g + 3 = i, f, g, o of units 16 g .. 16 g + 15
+int lstm_packed_row(int q);
+std::vector<float> to_lstm_fragments(const std::vector<float>& p, int K, int M);                        // {} unless M == 1024
 std::vector<float> pack_conv2d_bn(const std::vector<float>& p, int taps, int K, int M, const float* bias, const float* bn, std::vector<float>* bias_out);

@@ -40,6 +40,16 @@ def _i64(t, device):
     return t.to(device=device, dtype=torch.int64).contiguous()
 
 
+def _check_speaker_width(cfg, spk, B):
+    """spker_embeds as the speaker_emb dense takes them: [B, external_speaker_dim] (512: DeepSpeaker, 256: GE2E).  The kernel reads
+    external_speaker_dim floats per row whatever it is handed, so another width must stop here."""
+    if spk is None:
+        return
+    if spk.dim() < 1 or spk.shape[-1] != cfg.external_speaker_dim or spk.numel() != B * cfg.external_speaker_dim:
+        raise ValueError(f"spker_embeds has shape {tuple(spk.shape)}; this model's speaker_emb takes [{B}, {cfg.external_speaker_dim}] "
+                         f"(external_speaker_dim = {cfg.external_speaker_dim}: 512 for DeepSpeaker vectors, 256 for GE2E)")
+
+
 def _resolve_controls(B, L, p_control=1.0, e_control=1.0, d_control=1.0):
     """The three prosody controls of a call over B utterances padded to L phonemes, each a Python number (the scalar path), a [B]
     tensor (one factor per utterance) or a [B, L] tensor (one per phoneme), fp32.  Returns ((p, e, d) scalars, {"p" | "e" | "d":
@@ -429,6 +439,7 @@ class DurationPitchSpeakerNet(torch.nn.Module):
         spk_in = _f32(spker_embeds, dev) if (cfg.multi_speaker and not table and spker_embeds is not None) else None
         if cfg.multi_speaker and not table and spk_in is None:
             raise AssertionError("Speaker embedding should not be None")
+        _check_speaker_width(cfg, spk_in, B)
         spk_ids = None
         if table:
             if speakers is None:
@@ -2446,6 +2457,123 @@ def speaker_embedding(enc: SpeakerEncoder, wavs, lengths=None, sample_rate=22050
     return speaker_forward(enc, win, row_map, info.shape[0])
 
 
+# ---- GE2E speaker embeddings from reference audio (csrc/ge2e.hip; definition: cmtts_amd/ge2e.py)
+
+class GE2EEncoder:
+    """The GE2E LSTM encoder on the device (ge2e_encoder/inference.py: load_model): cmtts_ge2e_* behind one handle."""
+
+    def __init__(self, weights, device="cuda:0"):
+        from .weights import import_ge2e
+        self.device = _norm_device(device) if torch.cuda.is_available() else torch.device(device)
+        self.lib = _lib.load()
+        self._h = C.c_void_p()
+        _lib.check(self.lib.cmtts_ge2e_create(C.byref(self._h)))
+        self._ws = _Workspace()
+        self._ready = False
+        _push_state_dict(self.lib, self.lib.cmtts_ge2e_set_tensor, self._h, import_ge2e(weights))
+        if self.device.type == "cuda" and torch.cuda.is_available():
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.cmtts_ge2e_finalize(self._h))
+            self._ready = True
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and C is not None:
+            self.lib.cmtts_ge2e_destroy(h)
+            self._h = None
+
+    def _require(self):
+        if not self._ready:
+            raise RuntimeError("GE2EEncoder: no GPU — cmtts_amd has no CPU fallback (the weights are loaded, the kernels cannot run)")
+
+
+def get_ge2e_encoder(weights, device="cuda:0"):
+    """ge2e_encoder/inference.py: load_model — `weights`: a dict of the encoder's tensors under torch's names, an .npz of them, or the
+    reference's encoder.pt (weights.import_ge2e)."""
+    return GE2EEncoder(weights, device)
+
+
+def ge2e_features(enc: GE2EEncoder, wavs, lengths=None, sample_rate=22050, using_partials=True):
+    """cmtts_ge2e_features: float audio [B, n] (or a list of rows) at 22 050 Hz -> (windows fp32 [W, T, 40] on the device — the rows' partials,
+    T = 160, or with using_partials=False each row's whole power mel padded to the longest —, win_lens int32 [W] on the device, info int32
+    [B, 4] on the HOST = (samples, padded samples, frames, windows) per row).  Reading info back synchronises the stream."""
+    from . import ge2e as g2
+    enc._require()
+    if int(sample_rate) != g2.SAMPLE_RATE:
+        raise ValueError(f"ge2e_embedding: the audio must be at {g2.SAMPLE_RATE} Hz, the one sample rate the GE2E front end is defined at, not {sample_rate}")
+    dev = enc.device
+    if isinstance(wavs, (list, tuple)):
+        rows = [torch.as_tensor(np.asarray(w, np.float32)).reshape(-1) for w in wavs]
+        if lengths is None:
+            lengths = [r.numel() for r in rows]
+        wavs = torch.zeros(len(rows), max(1, max(r.numel() for r in rows)), dtype=torch.float32)
+        for i, r in enumerate(rows):
+            wavs[i, :r.numel()] = r
+    wavs = torch.as_tensor(wavs)
+    if wavs.dim() == 1:
+        wavs = wavs[None]
+    if not wavs.dtype.is_floating_point:
+        raise ValueError("ge2e_embedding: float audio expected")
+    wavs = _f32(wavs, dev)
+    B, n = wavs.shape
+    lens = _clip_lengths(lengths, B, n)
+    if using_partials:
+        mode, T, max_w = 1, g2.PARTIAL_FRAMES, max(len(g2.partial_slices(v)[1]) for v in lens)
+    else:
+        mode, T, max_w = 0, max(1, max(g2.frame_count(v) for v in lens)), 1
+    with torch.cuda.device(dev):
+        n_valid = torch.tensor(lens, dtype=torch.int32).to(dev)
+        win = torch.empty(B * max_w, T, g2.N_MELS, dtype=torch.float32, device=dev)
+        wl = torch.empty(B * max_w, dtype=torch.int32, device=dev)
+        info = torch.empty(B, 4, dtype=torch.int32, device=dev)
+        _lib.check(enc.lib.cmtts_ge2e_features(enc._h, _ptr(wavs), B, n, _ptr(n_valid), int(sample_rate), mode, max_w, T, _ptr(win), _ptr(wl),
+                                               _ptr(info), _stream()))
+        info = info.cpu().numpy()
+    W = int(info[:, 3].sum())
+    return win[:W], wl[:W], info
+
+
+def ge2e_forward(enc: GE2EEncoder, windows, row_map=None, rows=None, lengths=None):
+    """cmtts_ge2e_forward: windows fp32 [W, T, 40] (device), lengths int [W] or None, row_map int [W] (host) -> embeddings fp32 [rows, 256]
+    (device): per row the normalised mean of its windows' embeddings; row_map None: the W window embeddings themselves."""
+    enc._require()
+    dev = enc.device
+    windows = _f32(windows, dev)
+    W, T = int(windows.shape[0]), int(windows.shape[1])
+    rm = None
+    if row_map is not None:
+        rm = np.ascontiguousarray(np.asarray(row_map.cpu() if isinstance(row_map, torch.Tensor) else row_map, np.int32).reshape(-1))
+        if rm.size != W:
+            raise ValueError("ge2e_forward: one row_map entry per window")
+    rows = W if rows is None else int(rows)
+    with torch.cuda.device(dev):
+        ln = None
+        if lengths is not None:
+            ln = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).contiguous()
+            if ln.numel() != W:
+                raise ValueError("ge2e_forward: one length per window")
+        emb = torch.empty(rows, 256, dtype=torch.float32, device=dev)
+        nb = enc.lib.cmtts_ge2e_workspace_bytes(max(W, 1), max(T, 1))
+        ws = enc._ws.get("ge2e", nb, dev)
+        _lib.check(enc.lib.cmtts_ge2e_forward(enc._h, _ptr(windows) if W else None, W, max(T, 1), _ptr(ln), None if rm is None else rm.ctypes.data,
+                                              rows, _ptr(emb), _ptr(ws), nb, _stream()))
+    return emb
+
+
+def ge2e_embedding(enc: GE2EEncoder, wavs, lengths=None, sample_rate=22050, using_partials=True):
+    """ge2e_encoder/inference.py: embed_utterance for a batch — float audio [B, n] (or a list of 1-D arrays) at 22 050 Hz, as the reference
+    hands it over: RAW (preprocess_wav — volume normalisation, webrtcvad trim — is not applied on this path, speaker_embedder.py:51) -> a
+    DEVICE tensor [B, 256] of unit-norm GE2E vectors, accepted unchanged as spker_embeds= by a model whose external_speaker_dim is 256.
+    using_partials=False: each row's whole spectrogram through the network once."""
+    win, wl, info = ge2e_features(enc, wavs, lengths, sample_rate, using_partials)
+    bad = [b for b in range(info.shape[0]) if info[b, 3] == 0]
+    if bad:
+        raise ValueError(f"ge2e_embedding: rows {bad} hold no samples")
+    if not using_partials:
+        return ge2e_forward(enc, win, None, None, wl)
+    return ge2e_forward(enc, win, np.repeat(np.arange(info.shape[0], dtype=np.int32), info[:, 3]), info.shape[0])
+
+
 # ---- recorded speech in (csrc/mel_analysis.hip; definition: cmtts_amd/analysis.py; DESIGN.md §3.5i)
 
 class Analyzer:
@@ -2900,20 +3028,33 @@ def pitch_targets(pt: PitchTracker, wavs, lengths=None, check=True):
 
 
 class PreDefinedEmbedder(torch.nn.Module):
-    """model/speaker_embedder.py:11-42 — forward(audio) -> numpy (1, 512).  config: the preprocess YAML dict; the ResCNN's weights come from
-    `weights` (default: the reference's checkpoint path, which needs h5py; see weights.import_deepspeaker)."""
+    """model/speaker_embedder.py:11-42 — forward(audio) -> numpy (1, 512) for "DeepSpeaker", (1, 256) for "GE2E".  config: the preprocess YAML
+    dict.  DeepSpeaker: the ResCNN's weights come from `weights` (default: the reference's checkpoint path, which needs h5py; see
+    weights.import_deepspeaker).  GE2E: the LSTM encoder's from `weights` or config["preprocessing"]["ge2e_speaker_embedder_path"]
+    (weights.import_ge2e); the audio goes in raw, as in the reference (speaker_embedder.py:51)."""
 
-    def __init__(self, config, weights="./deepspeaker/pretrained_models/ResCNN_triplet_training_checkpoint_265.h5", device="cuda:0"):
+    _DEEPSPEAKER_CKPT = "./deepspeaker/pretrained_models/ResCNN_triplet_training_checkpoint_265.h5"
+
+    def __init__(self, config, weights=None, device="cuda:0"):
         super().__init__()
         self.sampling_rate = config["preprocessing"]["audio"]["sampling_rate"]
         self.win_length = config["preprocessing"]["stft"]["win_length"]
         self.embedder_type = config["preprocessing"]["speaker_embedder"]
-        if self.embedder_type != "DeepSpeaker":
+        if self.embedder_type == "DeepSpeaker":
+            self.embedder = get_speaker_encoder(self._DEEPSPEAKER_CKPT if weights is None else weights, device)
+        elif self.embedder_type == "GE2E":
+            if weights is None:
+                weights = config["preprocessing"].get("ge2e_speaker_embedder_path")
+            if weights is None:
+                raise ValueError('PreDefinedEmbedder: "GE2E" needs weights= or preprocessing.ge2e_speaker_embedder_path')
+            self.embedder = get_ge2e_encoder(weights, device)
+        else:
             raise NotImplementedError(f"speaker embedder {self.embedder_type!r}")
-        self.embedder = get_speaker_encoder(weights, device)
 
     def forward(self, audio):
         audio = np.asarray(audio.detach().cpu() if isinstance(audio, torch.Tensor) else audio, np.float32).reshape(1, -1)
+        if self.embedder_type == "GE2E":
+            return ge2e_embedding(self.embedder, audio, None, self.sampling_rate).cpu().numpy()
         return speaker_embedding(self.embedder, audio, None, self.sampling_rate, self.win_length).cpu().numpy()
 
 
@@ -2965,6 +3106,7 @@ def text_state_records(model: CMTotalTTS, texts, src_lens, lo, hi, spker_embeds=
     ids = _i64(speakers[lo:hi], dev) if table else None
     if cfg.multi_speaker and not table and spker_embeds is None:
         raise AssertionError("Speaker embedding should not be None")
+    _check_speaker_width(cfg, spk_in, hi - lo)
     if table:
         if speakers is None:
             raise AssertionError("speakers (ids into the speaker_emb table) should not be None")

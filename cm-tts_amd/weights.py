@@ -264,3 +264,57 @@ def import_deepspeaker(path_or_dict):
     if missing:
         raise KeyError(f"import_deepspeaker: {len(missing)} tensors missing, first {missing[0]!r}")
     return OrderedDict((n, out[n]) for n in want)
+
+
+GE2E_KEYS = tuple(f"lstm.{p}_l{l}" for l in range(3) for p in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")) + ("linear.weight", "linear.bias")
+
+
+def synth_ge2e_state_dict(seed: int = 0, scale: float = 1.0):
+    """State dict of the GE2E SpeakerEncoder (ge2e_encoder/model.py:12-24) under torch's names — `lstm.weight_ih_l0` (1024, 40),
+    `lstm.weight_hh_l2` (1024, 256), `lstm.bias_hh_l1` (1024,), `linear.weight` (256, 256), `linear.bias` — drawn like torch's own
+    initialiser, U(-1 / 16, 1 / 16) times `scale`, plus the two similarity scalars the inference path ignores."""
+    sd = OrderedDict()
+    k = scale / math.sqrt(256.0)
+
+    def U(name, shape):
+        sd[name] = ((_rs("ge2e." + name, seed).uniform(size=shape) * 2.0 - 1.0) * k).astype(np.float32)
+
+    for l in range(3):
+        U(f"lstm.weight_ih_l{l}", (1024, 40 if l == 0 else 256))
+        U(f"lstm.weight_hh_l{l}", (1024, 256))
+        U(f"lstm.bias_ih_l{l}", (1024,))
+        U(f"lstm.bias_hh_l{l}", (1024,))
+    U("linear.weight", (256, 256))
+    U("linear.bias", (256,))
+    sd["similarity_weight"] = np.asarray([10.0], np.float32)
+    sd["similarity_bias"] = np.asarray([-5.0], np.float32)
+    return sd
+
+
+def import_ge2e(path_or_dict):
+    """The GE2E encoder's weights as a flat dict of float32 arrays under torch's names.  Takes a dict (of arrays or tensors, optionally
+    wrapped as {"model_state": ...}), an .npz file, or the reference's encoder.pt (ge2e_encoder/inference.py:32-33:
+    torch.load(...)["model_state"]); `similarity_*` entries are ignored.  The real checkpoint is not available where this project is
+    developed: the .pt leg has run only on checkpoints written by the tests."""
+    if isinstance(path_or_dict, dict):
+        raw = dict(path_or_dict)
+    elif str(path_or_dict).endswith(".npz"):
+        raw = dict(np.load(path_or_dict))
+    else:
+        import torch
+        raw = torch.load(path_or_dict, map_location="cpu")
+    if "model_state" in raw:
+        raw = dict(raw["model_state"])
+    out = OrderedDict()
+    for n in GE2E_KEYS:
+        if n not in raw:
+            raise KeyError(f"import_ge2e: tensor {n!r} missing")
+        v = raw[n]
+        v = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        out[n] = np.ascontiguousarray(v, np.float32)
+        l = n[-1]
+        want = {"weight_ih": (1024, 40 if l == "0" else 256), "weight_hh": (1024, 256), "bias_ih": (1024,), "bias_hh": (1024,)}.get(
+            n.split(".")[1][:-3], (256, 256) if n == "linear.weight" else (256,))
+        if out[n].shape != want:
+            raise ValueError(f"import_ge2e: {n} has shape {out[n].shape}, expected {want}")
+    return out

@@ -70,6 +70,7 @@ const char* cmtts_version(void);
  * targets (cmtts_set_duration_targets, a new struct) with cmtts_phoneme_marks: entry points only, still 8.
  * Likewise the loudness measurement (cmtts_loudness_*) and cmtts_resample_encode_gain: entry points only, still 8.
  * Likewise the speaker encoder (cmtts_spkenc_*, a new opaque handle): entry points only, still 8.
+ * Likewise the GE2E speaker encoder (cmtts_ge2e_*, a new opaque handle): entry points only, still 8.
  * Likewise the recorded-speech analysis (cmtts_mel_basis, cmtts_analysis_*, cmtts_mel_analysis, cmtts_phoneme_energy, cmtts_pcm_crossfade): still 8.
  * Likewise the alignment of a recording to its phonemes (cmtts_align_*): entry points only, still 8.
  * Likewise the pitch of a recording (cmtts_pitch_*, a new opaque handle): entry points only, still 8.
@@ -559,6 +560,43 @@ int cmtts_spkenc_features(cmtts_spkenc* e, const float* wav, int rows, int64_t l
                           const int32_t* offsets, int max_windows, float* windows, int32_t* info, void* stream);
 int cmtts_spkenc_forward(cmtts_spkenc* e, const float* windows, int W, const int32_t* row_map, int rows, float* emb, void* ws, size_t ws_bytes,
                          void* stream);
+
+/* ---- GE2E speaker embeddings from reference audio (the definition in executable form: cmtts_amd/ge2e.py).
+ * The zero-shot path's other embedder (preprocess.yaml speaker_embedder: "GE2E"): the 256-d vector of a reference clip, on the device, fp32.
+ * Entry points only: CMTTS_ABI_VERSION stays 8.  The reference hands the raw 22 050 Hz waveform over: preprocess_wav (volume normalisation, the
+ * webrtcvad silence trim) is not applied on this path and is not part of these calls.
+ * cmtts_ge2e_create / _set_tensor / _finalize / _destroy replace ge2e_encoder/inference.py: load_model (SpeakerEncoder + load_state_dict of
+ *   checkpoint["model_state"], ge2e_encoder/model.py:12-24): tensors under torch's names — "lstm.weight_ih_l0" (1024, 40), "lstm.weight_hh_l1"
+ *   (1024, 256), "lstm.bias_ih_l2" (1024), "linear.weight" (256, 256), "linear.bias"; gate rows in torch's order i, f, g, o.  finalize packs the MFMA
+ *   fragment streams, sums the two biases, makes the windowed 551-point DFT table in double and uploads them.
+ * cmtts_ge2e_features replaces ge2e_encoder/audio.py: wav_to_mel_spectrogram and, for mode 1, inference.py: compute_partial_slices (58-107) with
+ *   the padding rule of embed_utterance (138-141): wav fp32 [rows][ld] (device) at fs = 22050 (anything else: CMTTS_E_INVALID), n_valid int32 [rows]
+ *   (device; clamped to [0, ld]) -> info int32 [rows][4] (device) = (n, the zero-padded length, its frames 1 + (n - 1) / 220, windows) and the
+ *   40-channel POWER mels (n_fft 551, hop 220, centred, reflect padding, periodic Hann, Slaney triangles on linspace(0, fs / 2, 276); no logarithm).
+ *   mode 1: windows fp32 [sum of windows][160][40], rows in order, a row's partials every 80 frames (the last one dropped below 75 % coverage unless
+ *   it is the only one), at most max_windows of them; win_lens int32 [windows] = 160.  mode 0: each row's whole spectrogram as one window
+ *   [rows][T][40], zero rows at and beyond its frames, win_lens = min(frames, T); max_windows must be 1.  A row with n = 0 has no window.
+ *   One launch, no allocation, no host synchronisation.
+ * cmtts_ge2e_forward replaces ge2e_encoder/model.py: SpeakerEncoder.forward (41-61) and the mean / norm of embed_utterance (147-149): windows fp32
+ *   [W][T][40] (device), lengths int32 [W] (device) or NULL (every window has T frames): a window's state stays as it is from its length on, what
+ *   the window holds there is not read into it.  row_map int32 [W] in HOST memory: the row each window belongs to, every entry in [0, rows) ->
+ *   emb fp32 [rows][256] (device) = the mean of a row's window embeddings relu(linear(h)) / (norm + 1e-5), divided by its L2 norm (no epsilon, as the
+ *   reference; zeros for a row without windows).  row_map NULL (rows == W): the window embeddings themselves, what embed_utterance returns with
+ *   using_partials = False.  A window's embedding does not depend on the other windows of the call.  ws: cmtts_ge2e_workspace_bytes(W, T) bytes (0
+ *   for rejected arguments; W T 5 KB: the gate pre-activations of one layer).  Seven or eight launches on `stream`, no allocation, no host
+ *   synchronisation.  No workgroup of the recurrence waits on another: a tile of windows is one workgroup from its first frame to its last.
+ * Null pointers, rows / ld / T < 1, W < 0, a row_map entry out of range, another sample rate or mode, a workspace that is too small, a handle that is
+ * not finalized: CMTTS_E_INVALID, checked before any launch. */
+typedef struct cmtts_ge2e cmtts_ge2e;
+int cmtts_ge2e_create(cmtts_ge2e** out);
+int cmtts_ge2e_set_tensor(cmtts_ge2e* e, const char* name, const float* data, const int64_t* shape, int ndim);
+int cmtts_ge2e_finalize(cmtts_ge2e* e);
+void cmtts_ge2e_destroy(cmtts_ge2e* e);
+size_t cmtts_ge2e_workspace_bytes(int W, int T);
+int cmtts_ge2e_features(cmtts_ge2e* e, const float* wav, int rows, int64_t ld, const int32_t* n_valid, int fs, int mode, int max_windows, int T,
+                        float* windows, int32_t* win_lens, int32_t* info, void* stream);
+int cmtts_ge2e_forward(cmtts_ge2e* e, const float* windows, int W, int T, const int32_t* lengths, const int32_t* row_map, int rows, float* emb, void* ws,
+                       size_t ws_bytes, void* stream);
 
 /* ---- recorded speech in (the definition in executable form: cmtts_amd/analysis.py).
  * The features the model was trained on, from a waveform, per request and on the device.  Entry points only: CMTTS_ABI_VERSION stays 8.
