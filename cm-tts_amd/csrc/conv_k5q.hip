@@ -20,7 +20,8 @@
 //     would walk all 256 rows alone).  An output element's products and their order do not depend on the split, so the form is taken at
 //     EVERY batch size and an utterance's pitch contour does not depend on the batch it is in (as for the FFN convs, conv_xres.hip WQ).
 // NOT bitwise the direct form (conv_xl_kernel / conv_xres_kernel): fp32 Winograd rounding, ~2e-6 of the activations per conv
-// (tests/test_gpu_parity.py::test_conv_k5q_kernel_vs_oracle; restated in oracle/winograd_ref.py: conv1d_f43_taps, k = 5).
+// (tests/test_gpu_parity.py::test_conv_k5q_kernel_vs_oracle; restated in oracle/winograd_ref.py: conv1d_f43_taps, k = 5; every instance and row
+// split alone against the float64 definition at the tile edges: tests/test_gpu_quad_kernels.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "resblock_pair.h"

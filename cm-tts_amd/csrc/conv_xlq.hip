@@ -21,7 +21,8 @@
 // formed in double, rounded once) stream L2 -> VGPR in iteration order [k-step][wave][point][64 lanes][4 m-tiles] through a buffer descriptor
 // (lane offset constant, step offset scalar) and a register ring; no barrier in the K loop.
 // NOT bitwise the direct form (fp32 Winograd; measured on the waveform next to the F(2,3) form in tests/test_gpu_parity.py); restated in
-// oracle/winograd_ref.py (conv1d_f43_taps) and checked against the plain conv on the CPU.
+// oracle/winograd_ref.py (conv1d_f43_taps; conv1d_f43_taps_dil for the residue classes) and checked against the plain conv on the CPU.  Every
+// instance alone against the float64 definition at its tile edges: tests/test_gpu_quad_kernels.py.
 #include <hip/hip_runtime.h>
 #include "resblock_pair.h"
 #include "xcd_map.h"
@@ -316,10 +317,12 @@ int launch_xlq_k(const ConvXlArgs& a, hipStream_t s) {
 }  // namespace
 
 // The conv in its F(4,3) form (a->wf = to_wino43_iter_fragments of the same weights).  Returns 0, -2 (shape not covered: C = 64 / 128 / 256,
-// k = 3 / 7 / 11, dilation 1 / 3 / 5, C_in = C; or a launch too small to pay for the transforms unless a->wino_force) or -3 (HIP error).
+// k = 3 / 7 / 11, dilation 1 / 3 / 5, C_in = C; x == y: in place a tile would read the halo its neighbour has already overwritten — vocoder.hip:
+// xl_pair never passes it, conv1 writes bT from x / bR and conv2 reads bT; y == res is fine; or a launch too small to pay for the transforms unless
+// a->wino_force) or -3 (HIP error).
 extern "C" int cmtts_launch_conv_xlq(const ConvXlArgs* a, void* stream_) {
     hipStream_t s = (hipStream_t)stream_;
-    if ((a->cin && a->cin != a->C) || a->T < 1 || a->B < 1) return -2;
+    if ((a->cin && a->cin != a->C) || a->T < 1 || a->B < 1 || a->x == a->y) return -2;
     if (!a->wino_force && (long)((a->T + 63) / 64) * a->B < 1024) return -2;
     if (a->C == 64) return launch_xlq_k<64>(*a, s);
     if (a->C == 128) return launch_xlq_k<128>(*a, s);

@@ -4,7 +4,7 @@ algebra the HIP kernels rely on is checked on the CPU against the plain convolut
   * denoiser_persist.hip, WINO instances (cm-tts_amd/csrc/weight_pack.cpp: to_wino_fragments): the gated k = 3, dilation-1 conv of
     ResidualBlock.forward (reference model/blocks.py:672) as F(2,3) over frame pairs;
   * conv_xlq.hip: conv_xlq_kernel (round 5): the dilation-1 ResBlock convs of HiFi-GAN as F(4,3) tap groups over output quads
-    (conv1d_f43_taps below);
+    (conv1d_f43_taps below; dilation 3 / 5 by residue classes: conv1d_f43_taps_dil; conv_xlq_pair.hip's k = 3 pair as the chain of two: pair_f43);
   * denoiser_persist.hip, WINO == 2 instances (round 5; weight_pack.cpp: to_wino43_fragments): the same conv as F(4,3) over frame quads
     (conv1d_f43 below: the kernel's transforms in the kernel's operation order);
   * resblock_pair.hip: conv_xlw_kernel (cm-tts_amd/csrc/resblock_pair.h: WinoTab<k>, weight_pack.cpp: to_wino_iter_fragments): the k = 3 / 7 / 11 dilated convs of
@@ -162,6 +162,30 @@ def conv1d_f43_taps(x, w, U=None):
     y[:, q0 + 2] = s12 + dt(4) * s34
     y[:, q0 + 3] = (d12 + dt(8) * d34) + M[5]
     return y[:, :T]
+
+
+def conv1d_f43_taps_dil(x, w, dil=1, U=None):
+    """conv_xlq_kernel at dilation 3 / 5 (conv_xlq.hip: residue classes): the outputs t = r (mod dil) are the UNDILATED same-padded conv on the class's
+    subsequence x[:, r::dil], so every class goes through conv1d_f43_taps on its own.  A tile holds 60 / dil = 20 or 12 entries per class, both
+    multiples of four and tiles start at multiples of 60: the kernel's quads are the subsequence's quads (entries 4 m .. 4 m + 3 of the class)."""
+    if dil == 1:
+        return conv1d_f43_taps(x, w, U)
+    y = np.zeros((w.shape[0], x.shape[1]), x.dtype)
+    U = f43_tap_weights(w) if U is None else U          # formed once for all classes
+    for r in range(min(dil, x.shape[1])):
+        y[:, r::dil] = conv1d_f43_taps(np.ascontiguousarray(x[:, r::dil]), w, U)
+    return y
+
+
+def pair_f43(x, w1, b1, w2, b2, dil, slope, U1=None, U2=None):
+    """A k = 3 ResBlock pair as the chain of two conv_xlq launches in their own products: xt = conv1(leaky(x)) + b1 at dilation dil (residue classes),
+    y = (conv2(leaky(xt)) + b2) + x at dilation 1 -> (y, xt), every operation in x's dtype.  conv_xlq_pair3_kernel forms the same products on conv1
+    quads that start one frame earlier (its tile's xt covers [t0 - 1, ..)): fp32 Winograd rounding apart from this chain, not a bit-for-bit twin."""
+    dt = x.dtype.type
+    act = lambda v: np.where(v > 0, v, v * dt(slope))
+    xt = conv1d_f43_taps_dil(act(x), w1, dil, U1) + b1.astype(x.dtype)[:, None]
+    y = (conv1d_f43_taps(act(xt), w2, U2) + b2.astype(x.dtype)[:, None]) + x
+    return y, xt
 
 
 # ---- the host-side weight packers (cm-tts_amd/csrc/weight_pack.cpp) as index expressions.  p: k-major weights [taps][K][M] (P[tap][input channel][output row]),

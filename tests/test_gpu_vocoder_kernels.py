@@ -293,13 +293,16 @@ def _convT(lib, stage, x, ldx, ldy, pre_div, mode, finite=True):
 KS, DILS = (3, 7, 11), (1, 3, 5)
 
 
-@pytest.mark.parametrize("k", KS)
-@pytest.mark.parametrize("Cc", [128, 256])
-@pytest.mark.parametrize("kernel", ["conv_xl", "conv_xlw"])
+# conv_xlw at C = 64 (one wave per workgroup with both m-tiles; production: dilation 5 of the C = 64 stage): k = 7 and 11 are all its launcher accepts
+# there.  cmtts_launch_conv_xl accepts C = 128 and 256 alone (C_in = 128 -> 256 at k = 5 apart): no instance below 128 to add.
+FP32_CONVS = [(kn, Cc, k) for kn in ("conv_xl", "conv_xlw") for Cc in (128, 256) for k in KS] + [("conv_xlw", 64, 7), ("conv_xlw", 64, 11)]
+
+
+@pytest.mark.parametrize("kernel,Cc,k", FP32_CONVS)
 def test_fp32_conv_vs_f64(kernel, Cc, k):
     """conv_xl_kernel (the direct form: the whole C = 32 .. 256 fp32 generator below the Winograd launch sizes) and conv_xlw_kernel (F(2,3) tap groups,
-    wino_force) alone: plain, with the residual, with y += and with both; conv_xl with its m-tile split on and off (same bits); conv_xlw also against the float32
-    restatement of its own products (oracle.winograd_ref.conv1d_winograd)."""
+    wino_force; C = 64 at k = 7 / 11 too) alone: plain, with the residual, with y += and with both; conv_xl with its m-tile split on and off (same bits); conv_xlw
+    also against the float32 restatement of its own products (oracle.winograd_ref.conv1d_winograd)."""
     lib = _clib()
     wino = kernel == "conv_xlw"
     w, b = VC.weights(Cc, Cc, k, 0)

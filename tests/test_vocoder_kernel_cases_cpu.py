@@ -106,7 +106,7 @@ def test_argument_blocks_match_the_headers():
 
 
 INSTANCES = ([("conv_xl", c, k, d, 0) for c in (128, 256) for k in (3, 7, 11) for d in (1, 3, 5)] +
-             [("conv_xlw", c, k, d, 0) for c in (128, 256) for k in (3, 7, 11) for d in (1, 3, 5)] +
+             [("conv_xlw", c, k, d, 0) for c in (128, 256) for k in (3, 7, 11) for d in (1, 3, 5)] + [("conv_xlw", 64, k, d, 0) for k in (7, 11) for d in (1, 3, 5)] +
              [(kn, c, k, d, 1) for kn, cs in (("conv16", (32, 64, 128)), ("conv_xl16", (128, 256)), ("resblock_pair", (32, 64)), ("resblock_pair16", (32, 64)),
                                              ("resblock_pairw16", (128,)), ("resblock_pair16x3", (32, 64, 128)), ("conv_xl16x3", (256,)))
               for c in cs for k in (3, 7, 11) for d in (1, 3, 5)] +
