@@ -1023,6 +1023,7 @@ extern "C" void cmtts_persist_set_debug(long long* dbg) { g_pdbg = dbg; }
 extern "C" long long* cmtts_persist_get_debug(void) { return g_pdbg; }
 
 extern "C" int cmtts_persist_chunks(int B, int T, int max_blocks) {
+    if (B < 1 || T < 1 || max_blocks < 1) return 0;
     const int tiles = (T + FN - 1) / FN;
     if (tiles > max_blocks) return 0;
     const int per_launch = max_blocks / tiles;
@@ -1033,7 +1034,7 @@ extern "C" int cmtts_persist_chunks(int B, int T, int max_blocks) {
 // caller's cross-stream guard has to reserve.  Mirrors the decisions of cmtts_launch_denoiser_persist(_lp).
 extern "C" int cmtts_persist_plan(int B, int T, int NL, int max_blocks, int force) {
     const int tiles = (T + FN - 1) / FN;
-    if (B < 1 || NL < 1 || NL > PERSIST_MAX_LAYERS || tiles > max_blocks || (long)C * T >= (1L << 30)) return 0;
+    if (B < 1 || T < 1 || max_blocks < 1 || NL < 1 || NL > PERSIST_MAX_LAYERS || tiles > max_blocks || (long)C * T >= (1L << 30)) return 0;
     if (!force && (long)tiles * B * 2 <= (long)max_blocks) return 0;
     const int per_launch = max_blocks / tiles;
     const int nchunks = (B + per_launch - 1) / per_launch;
@@ -1055,6 +1056,7 @@ extern "C" size_t cmtts_persist_halo_bytes(int B, int T) {
 extern "C" int cmtts_launch_denoiser_persist(const PersistArgs* a_in, int max_blocks, int force, void* stream_) {
     PersistArgs a = *a_in;
     hipStream_t stream = (hipStream_t)stream_;
+    if (a.B < 1 || a.T < 1 || max_blocks < 1) return -2;       // before tiles and the chunk count divide (force reaches here with any shape)
     const int tiles = (a.T + FN - 1) / FN;
     if (a.NL < 1 || a.NL > PERSIST_MAX_LAYERS || tiles > max_blocks || (long)C * a.T >= (1L << 30)) return -2;
     // a workgroup walks the whole stack alone (~128 us per layer): while the per-layer kernels can still spread the batch

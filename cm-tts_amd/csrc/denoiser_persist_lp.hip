@@ -488,6 +488,10 @@ int launch_mode(const PersistArgs& a, int tiles, int max_blocks, hipStream_t str
 extern "C" int cmtts_launch_denoiser_persist_lp(const PersistArgs* a_in, int mode, int max_blocks, int force, void* stream_) {
     PersistArgs a = *a_in;
     hipStream_t stream = (hipStream_t)stream_;
+    if (a.B < 1 || a.T < 1 || max_blocks < 1) return -2;       // before tiles and the chunk count divide (force reaches here with any shape)
+    // the 16-bit kernels read cp: a 16-bit model never brings factors (denoiser_side.hip: CondFactors::usable wants precision 0), and a caller
+    // that sets fact has left cp unfilled or null
+    if (a.fact) return -2;
     const int tiles = (a.T + FN - 1) / FN;
     if (a.NL < 1 || a.NL > PERSIST_MAX_LAYERS || tiles > max_blocks || (long)C * a.T >= (1L << 30) || mode < 1 || mode > 3) return -2;
     if (!force && (long)tiles * a.B * 2 <= (long)max_blocks) return -2;

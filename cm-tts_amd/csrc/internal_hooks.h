@@ -150,6 +150,11 @@ int cmtts_internal_k_mel_post_rows(const float* F, const float* xold, const floa
 int cmtts_internal_k_diff_embed(const float* t, const float* omega, float* emb, int B, int C, void* stream);
 int cmtts_internal_k_conv_post(const float* x, const float* w, const float* bias, float pre_div, float slope, float* wav, int B, int C, int T, int ld,
                                int KW, void* stream);
+// Test hook (kernel_hooks.hip; host only, never touches the GPU): sizeof PostRow, PersistGroup, PersistArgs and offsetof thirteen fields of PersistArgs and
+// five of PersistGroup (persist_args.h), in the order kernel_hooks.hip lists — what the ctypes mirrors of tests/persist_stack_cases.py are checked against
+// before tests/test_gpu_persist_stack.py hands them to the launchers of the persistent stack (exported like those of resblock_args.h).  Writes
+// min(n, 21) values, returns 21.
+int cmtts_internal_persist_args_layout(size_t* out, int n);
 #ifdef __cplusplus
 }
 #endif

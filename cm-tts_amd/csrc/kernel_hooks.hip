@@ -157,5 +157,21 @@ int cmtts_internal_ge2e_tail(const float* hlast, int W, const float* lin_t, cons
                              float* emb, void* stream) {
     return cmtts_launch_ge2e_tail(hlast, W, lin_t, lin_b, emb_w, row_map, rows, emb, stream);
 }
+// persist_args.h as THIS compiler lays it out (host only, no logic): tests/persist_stack_cases.py mirrors the three structs in ctypes and the
+// launchers of the persistent stack take PersistArgs from it.  out[0..2] = sizeof PostRow, PersistGroup, PersistArgs; then offsetof PersistArgs'
+// W3f, halo, cp_bstride, tail, skip_div, post_rows, fact, p1t, wino, xst, n_groups, grp, desc; then PersistGroup's cp_bstride, B, p1, ldp, xst.
+// Writes min(n, 21) values and returns how many there are.
+int cmtts_internal_persist_args_layout(size_t* out, int n) {
+    const size_t v[] = {sizeof(PostRow), sizeof(PersistGroup), sizeof(PersistArgs),
+                        offsetof(PersistArgs, W3f), offsetof(PersistArgs, halo), offsetof(PersistArgs, cp_bstride), offsetof(PersistArgs, tail),
+                        offsetof(PersistArgs, skip_div), offsetof(PersistArgs, post_rows), offsetof(PersistArgs, fact), offsetof(PersistArgs, p1t),
+                        offsetof(PersistArgs, wino), offsetof(PersistArgs, xst), offsetof(PersistArgs, n_groups), offsetof(PersistArgs, grp),
+                        offsetof(PersistArgs, desc),
+                        offsetof(PersistGroup, cp_bstride), offsetof(PersistGroup, B), offsetof(PersistGroup, p1), offsetof(PersistGroup, ldp),
+                        offsetof(PersistGroup, xst)};
+    const int have = (int)(sizeof(v) / sizeof(v[0]));
+    for (int i = 0; i < n && i < have; ++i) out[i] = v[i];
+    return have;
+}
 
 }  // extern "C"

@@ -109,9 +109,11 @@ extern "C" {
 size_t cmtts_persist_halo_bytes(int B, int T);
 size_t cmtts_persist_state_floats(int B, int T);   // PersistArgs.xst / PersistGroup.xst of a (B, T) batch
 // max_blocks = workgroups that are certainly co-resident (the CU count).  0 = launched, -2 = shape not
-// supported or (unless force) too small to pay off: the caller uses the per-layer kernels, -3 = HIP error.
+// supported (B < 1, T < 1 and max_blocks < 1 included, with or without force) or (unless force) too small to pay off: the caller uses the
+// per-layer kernels, -3 = HIP error.
 int cmtts_launch_denoiser_persist(const PersistArgs* a, int max_blocks, int force, void* stream);
-// 16-bit operand variant (denoiser_persist_lp.hip): mode 1 = bf16, 2 = fp16; W3f / Wof = 16-bit fragment-order weights.
+// 16-bit operand variant (denoiser_persist_lp.hip): mode 1 = bf16, 2 = fp16, 3 = fp16x3; W3f / Wof = 16-bit fragment-order weights.  Reads cp:
+// a->fact != 0 returns -2; ignores wino and n_groups.
 int cmtts_launch_denoiser_persist_lp(const PersistArgs* a, int mode, int max_blocks, int force, void* stream);
 // Ragged form: a->n_groups, a->grp[], a->n_wg, a->desc[] filled by the caller (denoiser_side.hip: cmtts_sample_ragged); the halo granules of every
 // group must already be cleared on `stream`.  0 = launched, -2 = not supported, -3 = HIP error.

@@ -1,7 +1,8 @@
 """The consistency denoiser's kernels called ALONE through their launch hooks (cm-tts_amd/csrc/resblock_args.h, cond_gemm.h, inproj.h) against the
 float64 definition of the same operation (tests/denoiser_kernel_cases.py): the element-wise check of the denoiser that the whole-network criteria
 of tests/test_gpu_precision.py and the kernel-against-kernel bit comparisons (fused = three-launch, split = fused, persistent = per-layer, F(4,3)
-per-layer = persistent) rest on.  Those comparisons carry this anchor over to the persistent stack, which is not called here.
+per-layer = persistent) rest on.  The persistent stack is called alone in tests/test_gpu_persist_stack.py, against its own float64 definition and bit
+for bit against chains of the per-layer launches anchored here.
 
   A  the fp32 residual block, its two halves anchored separately: resblock_split_out on a given z; resblock_split (z, x', skip);
      resblock_fused_kernel<32> and <64> (cmtts_resblock_set_tile) bit for bit the split form and within the bound; resblock_w43 (F(4,3)) with and
