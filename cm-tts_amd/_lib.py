@@ -148,6 +148,14 @@ SIGNATURES = {
     "cmtts_pitch_nacf": (_i, [_vp, _vp, _i, _i, _i64, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_pitch_track": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_pitch_targets": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cmtts_metric_dct_table": (_i, [_i, _i, _vp]),
+    "cmtts_metric_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cmtts_metric_cepstra": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "cmtts_metric_cost": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "cmtts_metric_diagonal": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "cmtts_metric_f0": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "cmtts_metric_ssim_prepare": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "cmtts_metric_ssim": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "cmtts_profile_begin": (_i, [_i, _i]),
     "cmtts_set_fused_resblock": (_i, [_i]),
     "cmtts_set_persistent_denoiser": (_i, [_i]),

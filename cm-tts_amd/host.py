@@ -3027,6 +3027,175 @@ def pitch_targets(pt: PitchTracker, wavs, lengths=None, check=True):
     return pitch_targets_from_f0(pt, p["f0"], p["frames"], check=check)
 
 
+# ---- objective metrics of a rendering against its recording (csrc/metrics.hip; definition: cmtts_amd/metrics.py)
+
+_METRIC_WS = _Workspace()
+_METRIC_TABLES = {}      # (device, n_cep) -> the DCT table on that device
+_METRIC_KEEP = {}        # per device: the host lengths of the latest call, read by the DTW's copies on the stream
+
+
+def _metric_table(lib, dev, n_cep):
+    key = (str(dev), n_cep)
+    if key not in _METRIC_TABLES:
+        from . import metrics as M
+        tab = np.empty((M.N_MELS, n_cep), np.float32)
+        _lib.check(lib.cmtts_metric_dct_table(M.N_MELS, n_cep, C.c_void_p(tab.ctypes.data)))
+        _METRIC_TABLES[key] = torch.from_numpy(tab).to(dev)
+    return _METRIC_TABLES[key]
+
+
+def _metric_lengths(what, lens, B, side, lo=1):
+    lens = [int(v) for v in (lens.tolist() if hasattr(lens, "tolist") else lens)]
+    if len(lens) != B or any(v < lo or v > side for v in lens):
+        raise ValueError(f"{what}: one length in [{lo}, {side}] per row expected, not {lens}")
+    return lens
+
+
+def _metric_device(device, *tensors):
+    if device is None:
+        device = next((t.device for t in tensors if isinstance(t, torch.Tensor) and t.is_cuda), "cuda:0")
+    if not torch.cuda.is_available():
+        raise RuntimeError("metrics: no GPU — cmtts_amd has no CPU fallback (metrics.py is the definition the kernels are tested against)")
+    return _norm_device(device)
+
+
+def mel_cepstra(mel, lens, n_cep=20, device=None):
+    """The cepstra the metrics are made of (cmtts_metric_cepstra, one launch): mel [B, T, 80] natural-log mel (mel_from_audio, or the model's
+    rendering), lens [B] frames per row (0 .. T) -> fp32 [B, T, n_cep] on the device, the orthonormal DCT-II over the mel channels; rows at
+    and beyond a row's frames are zeros.  The table is made once per device and n_cep.  These are NOT WORLD / SPTK mel-cepstra (metrics.py)."""
+    from . import metrics as M
+    B, T, _ = _align_mel("mel_cepstra: mel", mel)
+    n_cep = int(n_cep)
+    if not 1 <= n_cep <= M.N_MELS:
+        raise ValueError(f"mel_cepstra: 1 <= n_cep <= {M.N_MELS}, not {n_cep}")
+    lens = _metric_lengths("mel_cepstra: lens", lens, B, T, lo=0)
+    dev, lib = _metric_device(device, mel), _lib.load()
+    x = _f32(mel, dev)
+    with torch.cuda.device(dev):
+        ld = torch.tensor(lens, dtype=torch.int32).to(dev)
+        out = torch.zeros(B, T, n_cep, dtype=torch.float32, device=dev)
+        _lib.check(lib.cmtts_metric_cepstra(_ptr(x), _ptr(ld), _ptr(_metric_table(lib, dev, n_cep)), B, T, M.N_MELS, n_cep, _ptr(out), _stream()))
+    return out
+
+
+def score_pairs(mel_syn, syn_lens, mel_rec, rec_lens, f0_syn=None, f0_rec=None, align="dtw", mcd_coefs=(1, 13), ssim_coefs=20, data_range=None,
+                emb_syn=None, emb_rec=None, device=None):
+    """How close B renderings are to the recordings they were made from (cmtts_metric_*, cmtts_align_dtw; the definition: metrics.py, which says
+    where this differs from the reference's all_metrics.py).  mel_syn [B, Ts, 80], syn_lens [B]; mel_rec [B, Tr, 80], rec_lens [B] (mel_from_audio);
+    f0_syn [B, Ts], f0_rec [B, Tr] in Hz with 0 = unvoiced (pitch_from_audio), both or neither.  align="dtw": the exact DTW of align.py on the
+    cepstral cost; "frame": frame i against frame i.  mcd_coefs (k_lo, k_hi): the cepstra of the distortion (c0 excluded by default);
+    ssim_coefs: the first C cepstra make the images; data_range: the SSIM's L (default: max - min over the pairs of this call, taken on the
+    device).  Returns device tensors [B]: "mcd" (dB, of this project's cepstra), "ssim", "path_len", "row" int32 [B, Tr] (the rendering frame
+    per recording frame); with F0 "ffe", "gpe", "vde", "f0_rmse_cents", "f0_mae_cents", "f0_corr" (NaN where undefined) and "counts" int32
+    [B, 4] = (n, n_vv, n_gpe, n_vde); with emb_syn, emb_rec [B, D] "speaker_cos" (all_metrics.py:562-602).  Nothing is copied to the host.
+    Shapes and lengths that do not fit raise ValueError before a device is asked for."""
+    from . import metrics as M
+    B, Ts, _ = _align_mel("score_pairs: mel_syn", mel_syn)
+    Br, Tr, _ = _align_mel("score_pairs: mel_rec", mel_rec)
+    if Br != B:
+        raise ValueError(f"score_pairs: {B} renderings and {Br} recordings")
+    if B > 65535:
+        raise ValueError("score_pairs: at most 65535 pairs per call")
+    xl = _metric_lengths("score_pairs: syn_lens", syn_lens, B, Ts)
+    yl = _metric_lengths("score_pairs: rec_lens", rec_lens, B, Tr)
+    if align not in ("dtw", "frame"):
+        raise ValueError(f"score_pairs: align = {align!r}: expected 'dtw' or 'frame'")
+    if (f0_syn is None) != (f0_rec is None):
+        raise ValueError("score_pairs: f0_syn and f0_rec go together")
+    if f0_syn is not None and (tuple(f0_syn.shape) != (B, Ts) or tuple(f0_rec.shape) != (B, Tr)):
+        raise ValueError(f"score_pairs: f0_syn [{B}, {Ts}] and f0_rec [{B}, {Tr}] expected, not {tuple(f0_syn.shape)}, {tuple(f0_rec.shape)}")
+    if (emb_syn is None) != (emb_rec is None):
+        raise ValueError("score_pairs: emb_syn and emb_rec go together")
+    if emb_syn is not None and (len(emb_syn.shape) != 2 or tuple(emb_syn.shape) != tuple(emb_rec.shape) or emb_syn.shape[0] != B):
+        raise ValueError(f"score_pairs: emb_syn and emb_rec must both be [{B}, D], not {tuple(emb_syn.shape)}, {tuple(emb_rec.shape)}")
+    k_lo, k_hi = (int(v) for v in mcd_coefs)
+    C_img = int(ssim_coefs)
+    if not 0 <= k_lo <= k_hi < M.N_MELS or not 1 <= C_img <= M.N_MELS:
+        raise ValueError(f"score_pairs: mcd_coefs {mcd_coefs} must lie in 0 .. {M.N_MELS - 1} and ssim_coefs {ssim_coefs} in 1 .. {M.N_MELS}")
+    if data_range is not None and not float(data_range) > 0.0:
+        raise ValueError("score_pairs: data_range must be positive")
+    n_cep = max(k_hi + 1, C_img)
+    dev, lib = _metric_device(device, mel_syn, mel_rec), _lib.load()
+    x, y = _f32(mel_syn, dev), _f32(mel_rec, dev)
+    xl_h, yl_h = np.asarray(xl, np.int32), np.asarray(yl, np.int32)
+    _METRIC_KEEP[dev] = (xl_h, yl_h)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    with torch.cuda.device(dev):
+        st = _stream()
+        tab = _metric_table(lib, dev, n_cep)
+        xl_d, yl_d = torch.from_numpy(xl_h).to(dev), torch.from_numpy(yl_h).to(dev)
+        cx = torch.zeros(B, Ts, n_cep, dtype=torch.float32, device=dev)
+        cy = torch.zeros(B, Tr, n_cep, dtype=torch.float32, device=dev)
+        _lib.check(lib.cmtts_metric_cepstra(_ptr(x), _ptr(xl_d), _ptr(tab), B, Ts, M.N_MELS, n_cep, _ptr(cx), st))
+        _lib.check(lib.cmtts_metric_cepstra(_ptr(y), _ptr(yl_d), _ptr(tab), B, Tr, M.N_MELS, n_cep, _ptr(cy), st))
+        cost = torch.empty(B, Ts, Tr, dtype=torch.float32, device=dev)
+        _lib.check(lib.cmtts_metric_cost(_ptr(cx), _ptr(xl_d), Ts, _ptr(cy), _ptr(yl_d), Tr, B, n_cep, k_lo, k_hi, _ptr(cost), st))
+        total = torch.empty(B, dtype=torch.float32, device=dev)
+        n = torch.empty(B, dtype=torch.int32, device=dev)
+        if align == "dtw":
+            row = torch.zeros(B, Tr, dtype=torch.int32, device=dev)
+            nb = lib.cmtts_align_workspace_bytes(B, Ts, Tr)
+            ws = _ALIGN_WS.get("align", nb, dev)
+            _lib.check(lib.cmtts_align_dtw(_ptr(cost), hp(xl_h), hp(yl_h), B, Ts, Tr, _ptr(row), _ptr(total), _ptr(n), _ptr(ws), nb, st))
+            row_arg = _ptr(row)
+        else:
+            _lib.check(lib.cmtts_metric_diagonal(_ptr(cost), _ptr(xl_d), _ptr(yl_d), B, Ts, Tr, _ptr(total), _ptr(n), st))
+            j = torch.arange(Tr, dtype=torch.int32, device=dev)[None, :]
+            row = torch.where(j < yl_d[:, None], torch.minimum(j, xl_d[:, None] - 1), torch.zeros_like(j))
+            row_arg = None
+        out = {"mcd": (total.double() * M.MCD_CONST / n.double()).float(), "row": row, "path_len": n}
+        u = torch.empty(B, Tr, C_img, dtype=torch.float32, device=dev)
+        v = torch.empty(B, Tr, C_img, dtype=torch.float32, device=dev)
+        mm = torch.empty(B, 2, dtype=torch.float32, device=dev)
+        _lib.check(lib.cmtts_metric_ssim_prepare(_ptr(cx), _ptr(xl_d), Ts, _ptr(cy), _ptr(yl_d), Tr, row_arg, B, n_cep, C_img, _ptr(u), _ptr(v),
+                                                 _ptr(mm), st))
+        if data_range is None:
+            rng = (mm[:, 1].max() - mm[:, 0].min()).reshape(1)
+        else:
+            rng = torch.full((1,), float(data_range), dtype=torch.float32, device=dev)
+        ssim = torch.empty(B, dtype=torch.float32, device=dev)
+        nb = lib.cmtts_metric_workspace_bytes(B, Tr, C_img)
+        ws = _METRIC_WS.get("ssim", nb, dev)
+        _lib.check(lib.cmtts_metric_ssim(_ptr(u), _ptr(v), _ptr(yl_d), B, Tr, C_img, _ptr(rng), _ptr(ssim), _ptr(ws), nb, st))
+        out["ssim"], out["data_range"] = ssim, rng
+        if f0_syn is not None:
+            fs, fr = _f32(f0_syn, dev), _f32(f0_rec, dev)
+            counts = torch.empty(B, 4, dtype=torch.int32, device=dev)
+            vals = torch.empty(B, 3, dtype=torch.float32, device=dev)
+            _lib.check(lib.cmtts_metric_f0(_ptr(fs), _ptr(xl_d), Ts, _ptr(fr), _ptr(yl_d), Tr, row_arg, B, _ptr(counts), _ptr(vals), st))
+            c = counts.double()
+            out["counts"] = counts
+            out["ffe"], out["gpe"], out["vde"] = ((c[:, 2] + c[:, 3]) / c[:, 0]).float(), (c[:, 2] / c[:, 1]).float(), (c[:, 3] / c[:, 0]).float()
+            out["f0_rmse_cents"], out["f0_mae_cents"], out["f0_corr"] = vals[:, 0], vals[:, 1], vals[:, 2]
+        if emb_syn is not None:
+            out["speaker_cos"] = torch.nn.functional.cosine_similarity(_f32(emb_syn, dev), _f32(emb_rec, dev), dim=1)
+    return out
+
+
+def score_audio(an: Analyzer, pt: PitchTracker, wav_syn, wav_rec, lengths_syn=None, lengths_rec=None, **kw):
+    """score_pairs on two batches of audio at 22050 Hz (float in [-1, 1] or int16, [B, n] or lists of rows): mel_from_audio(pad="reference") and
+    pitch_from_audio for both sides, everything on the device.  The two analyses must agree on every row's frame count (they do at hop 256:
+    1 + n // 256); otherwise ValueError.  **kw: score_pairs' align, mcd_coefs, ssim_coefs, data_range, emb_syn, emb_rec."""
+    from . import analysis as A
+    sides = []
+    for what, wav, lengths in (("wav_syn", wav_syn, lengths_syn), ("wav_rec", wav_rec, lengths_rec)):
+        wav, lens = _audio_rows(wav, lengths, f"score_audio: {what}")
+        mel_frames = [A.frame_count(v, "reference") for v in lens]
+        f0_frames = [pt.geometry.frame_count(v) for v in lens]
+        if mel_frames != f0_frames:
+            raise ValueError(f"score_audio: {what}: the mel analysis gives {mel_frames} frames and the pitch analysis {f0_frames}")
+        sides.append((wav, lens, mel_frames))
+    if len(sides[0][1]) != len(sides[1][1]):
+        raise ValueError(f"score_audio: {len(sides[0][1])} renderings and {len(sides[1][1])} recordings")
+    feats = []
+    for wav, lens, frames in sides:
+        m = mel_from_audio(an, wav, lens, pad="reference")
+        p = pitch_from_audio(pt, wav, lens)
+        feats.append((m["mel"], frames, p["f0"]))
+    (ms, ls, fs), (mr, lr, fr) = feats
+    return score_pairs(ms, ls, mr, lr, f0_syn=fs, f0_rec=fr, device=an.device, **kw)
+
+
 class PreDefinedEmbedder(torch.nn.Module):
     """model/speaker_embedder.py:11-42 — forward(audio) -> numpy (1, 512) for "DeepSpeaker", (1, 256) for "GE2E".  config: the preprocess YAML
     dict.  DeepSpeaker: the ResCNN's weights come from `weights` (default: the reference's checkpoint path, which needs h5py; see

@@ -74,6 +74,7 @@ const char* cmtts_version(void);
  * Likewise the recorded-speech analysis (cmtts_mel_basis, cmtts_analysis_*, cmtts_mel_analysis, cmtts_phoneme_energy, cmtts_pcm_crossfade): still 8.
  * Likewise the alignment of a recording to its phonemes (cmtts_align_*): entry points only, still 8.
  * Likewise the pitch of a recording (cmtts_pitch_*, a new opaque handle): entry points only, still 8.
+ * Likewise the objective metrics of a rendering against its recording (cmtts_metric_*): entry points only, still 8.
  * A host compares cmtts_abi_version() with the CMTTS_ABI_VERSION it was built
  * against before it passes a struct (cmtts_amd/_lib.py does at load time). */
 #define CMTTS_ABI_VERSION 8
@@ -723,6 +724,60 @@ int cmtts_pitch_track(cmtts_pitch* p, const float* r, const float* pk, const int
                       size_t ws_bytes, void* stream);
 int cmtts_pitch_targets(cmtts_pitch* p, const float* f0, const int32_t* frames, int B, int T, float* cwt_spec, float* f0_mean, float* f0_std,
                         uint8_t* uv, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- objective metrics of a rendering against the recording it was made from (the definition in
+ * executable form: cmtts_amd/metrics.py).  Entry points only: CMTTS_ABI_VERSION stays 8.  They stand in for the reference's evaluation,
+ * all_metrics.py: Cal.get_all (SSIM, FFE, MCD), which needs librosa, pyworld, pysptk, fastdtw, pymcd and torchmetrics; the public recipes are
+ * restated on the features this library already makes on the device.  The cepstra are the orthonormal DCT-II of the 80-channel natural-log
+ * mel of cmtts_mel_analysis, NOT WORLD / SPTK mel-cepstra (all_metrics.py:401-408): an MCD from here is comparable within this project only.
+ * Every pointer is device memory unless it says host; x_len, y_len, lens: int32 [B] on the DEVICE (clamped to [1, side]; cmtts_metric_cepstra:
+ * [0, T]).  Frames, cells and rows at or beyond a pair's lengths are neither read nor written.  No atomics; a pair's result does not depend
+ * on what it is batched with.  No allocation, no host synchronisation.
+ * cmtts_metric_dct_table: pure host, never touches the GPU: table fp32 [80][n_cep] (HOST), D[n][0] = sqrt(1/80), D[n][k] = sqrt(2/80)
+ *   cos(pi (n + 1/2) k / 80), made in double and rounded once; the caller copies it to the device once.
+ * cmtts_metric_cepstra: mel fp32 [B][T][80] -> cepstra fp32 [B][T][n_cep], c[t][k] = sum_n mel[t][n] table[n][k], one fused fp32 chain of 80
+ *   terms (within 82 * 2^-24 * sum_n |mel| |D| of the exact sum).  One launch.
+ * cmtts_metric_cost replaces log_spec_dB_dist without its constant (all_metrics.py:396-399): cx fp32 [B][Ts][n_cep], cy fp32 [B][Tr][n_cep] ->
+ *   cost fp32 [B][Ts][Tr], the layout cmtts_align_dtw takes: c[i][j] = sqrt(sum_{k_lo <= k <= k_hi} (cx[i][k] - cy[j][k])^2) in the difference
+ *   form, one fused chain and a correctly rounded square root: relative error <= (K / 2 + 2) * 2^-24, K = k_hi - k_lo + 1; exactly 0 where
+ *   both frames are equal.  One launch.  cmtts_align_dtw on this matrix gives row, total and path_len of pymcd's "dtw" mode
+ *   (all_metrics.py:447-452); the MCD is (10 sqrt 2 / ln 10) total / path_len.
+ * cmtts_metric_diagonal: the frame-by-frame mode (no DTW): total fp32 [B] = the fp32 sum of c[j][j], j ascending, over path_len int32 [B] =
+ *   min(x_len, y_len) frames.  One launch.
+ * cmtts_metric_f0 replaces metrics/f0_frame_error.py:37-57 and compute_f0_corr / compute_f0_rmse (all_metrics.py:306-333): f0_syn fp32 [B][Ts],
+ *   f0_rec fp32 [B][Tr] in Hz with 0 = unvoiced (cmtts_pitch_track), row int32 [B][Tr] as cmtts_align_dtw wrote it (entries clamped to
+ *   [0, x_len)) or NULL: row[j] = min(j, x_len - 1).  Over the recording's frames j < y_len with i = row[j]: counts int32 [B][4] = (n = y_len,
+ *   n_vv: voiced on both sides, n_gpe: both voiced and |f_syn - f_rec| > 0.2f * f_rec in fp32 — one multiply, one subtract, one compare; the
+ *   reference divides: |est / (true + 1e-8) - 1| > 0.2 —, n_vde: exactly one side voiced), bit for bit the definition; vals fp32 [B][3] =
+ *   (rmse_cents, mae_cents, corr) over the both-voiced frames with e = 1200 log2(f_syn / f_rec), in double and in the definition's order,
+ *   rounded once; NaN for n_vv = 0 and, for corr, a zero variance.  FFE = (n_gpe + n_vde) / n, GPE = n_gpe / n_vv, VDE = n_vde / n.  One launch.
+ * cmtts_metric_ssim_prepare replaces all_metrics.py:365-371 on the recording's time axis: a[j] = cx[row[j]][0 .. C), b[j] = cy[j][0 .. C)
+ *   (row may be NULL as above), every column divided by its L2 norm over the y_len frames (norm in double: four interleaved partial sums
+ *   joined (0 + 1) + (2 + 3); the quotient in double, rounded once; a zero column stays zero) -> u, v fp32 [B][Tr][C], minmax fp32 [B][2] = the
+ *   min and max over the pair's u and v.  One launch.
+ * cmtts_metric_ssim replaces torchmetrics' StructuralSimilarityIndexMeasure as all_metrics.py:379-387 uses it (Wang et al. 2004: 11 x 11
+ *   Gaussian window, sigma 1.5, C1 = (0.01 L)^2, C2 = (0.03 L)^2, only the (y_len - 10) x (C - 10) windows inside the image): range points to
+ *   ONE fp32 on the device, the data range L (the reference: max - min over the corpus), so no host synchronisation lies between the two
+ *   calls -> ssim fp32 [B]: the five moments, the index and its mean in double, rounded once; NaN for y_len < 11 or C < 11.  Two launches.
+ *   ws: cmtts_metric_workspace_bytes(B, Tr, C) bytes (0 for B outside [1, 65535], Tr outside [1, 4096], C outside [1, 80]): one partial sum
+ *   per pair and 8 window rows.
+ * Refused before the GPU is touched (CMTTS_E_INVALID, message in cmtts_last_error): a null pointer (row excepted), B outside [1, 65535], a
+ * side outside [1, 4096], n_mels != 80, n_cep or C outside [1, 80], C > n_cep, not 0 <= k_lo <= k_hi < n_cep; a workspace that is too
+ * small: CMTTS_E_WORKSPACE. */
+int cmtts_metric_dct_table(int n_mels, int n_cep, float* table);
+size_t cmtts_metric_workspace_bytes(int B, int Tr, int C);
+int cmtts_metric_cepstra(const float* mel, const int32_t* lens, const float* table, int B, int T, int n_mels, int n_cep, float* cepstra,
+                         void* stream);
+int cmtts_metric_cost(const float* cx, const int32_t* x_len, int Ts, const float* cy, const int32_t* y_len, int Tr, int B, int n_cep, int k_lo,
+                      int k_hi, float* cost, void* stream);
+int cmtts_metric_diagonal(const float* cost, const int32_t* x_len, const int32_t* y_len, int B, int Ts, int Tr, float* total, int32_t* path_len,
+                          void* stream);
+int cmtts_metric_f0(const float* f0_syn, const int32_t* x_len, int Ts, const float* f0_rec, const int32_t* y_len, int Tr, const int32_t* row, int B,
+                    int32_t* counts, float* vals, void* stream);
+int cmtts_metric_ssim_prepare(const float* cx, const int32_t* x_len, int Ts, const float* cy, const int32_t* y_len, int Tr, const int32_t* row, int B,
+                              int n_cep, int C, float* u, float* v, float* minmax, void* stream);
+int cmtts_metric_ssim(const float* u, const float* v, const int32_t* y_len, int B, int Tr, int C, const float* range, float* ssim, void* ws,
+                      size_t ws_bytes, void* stream);
 
 /* ---- measurement hook (no reference counterpart; the reference's only perf tooling is the
  * wall-clock Timer of p_rtf_cm.py:64-108): HIP events recorded on the launch stream around every
