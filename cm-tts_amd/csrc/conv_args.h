@@ -86,9 +86,14 @@ extern "C" {
 // Chooses the tile configuration from (M, N, taps*|dil|) and launches on `stream`.  epi = ConvEpi.
 // Returns 0 or a negative cmtts status.
 int cmtts_launch_conv(const ConvArgs* a, int epi, int nbatch, void* stream);
-// 16-bit-operand variant (conv_mfma16.hip): wfrag = fragment-order weights, mode 1 = bf16, 2 = fp16.
+// 16-bit-operand variant (conv_mfma16.hip): wfrag = fragment-order weights, mode 1 = bf16, 2 = fp16, 3 = fp16x3.  Two epilogues: the ResBlock convs'
+// (bias [+ residual] [+ accumulate]) or, with a->text_epi, the text side's ([bias], alpha, none / ReLU / GELU, [+ residual], [length mask]; modes 1 and 2).
+// -2 = not covered, nothing launched; an empty launch (M, N or nbatch <= 0) returns 0.
 int cmtts_launch_conv16(const ConvArgs* a, const void* wfrag, int mode, int nbatch, void* stream);
-// X-resident form for the text side's K = 256 convs (conv_xt16.hip; tried first by cmtts_launch_conv16 when a->text_epi; same bits); -2 = not covered
+// X-resident form for the text side's K = 256 convs (conv_xt16.hip; tried first by cmtts_launch_conv16 when a->text_epi; same bits).  -2 = not covered,
+// nothing launched.  It refuses: text_epi == 0; K != 256; M no multiple of 128; taps outside {1, 3, 5, 9}; dil != 1; pad != (taps - 1) / 2; pre_div or
+// pre_slope != 1; zdiv != 1; split != INT_MAX; x16 or y16; a mode other than 1 and 2; K * ldx >= 2^31; M, N or nbatch <= 0; and in out[0]: ostride != 1, an
+// output offset, row_off, div != 1, rmul != 0, accum, bvec, Tout != N, an activation other than none / ReLU / GELU.  (tests/test_gpu_text16_kernels.py)
 int cmtts_launch_conv_xt16(const ConvArgs* a, const void* wfrag, int mode, int nbatch, void* stream);
 // X-resident variant for short sequences (conv_xres.hip): wfrag = fp32 fragment-order weights; -2 = unsupported.
 int cmtts_launch_conv_xres(const ConvArgs* a, const float* wfrag, int nbatch, void* stream);

@@ -287,8 +287,11 @@ int launch16(const ConvArgs& a, const void* wfrag, int mode, int nbatch, hipStre
 
 // Plain Conv1d with 16-bit operands: a->A is ignored, `wfrag` = fragment-order weights
 // [taps][ceil(K/16)][ceil(M/32)][64][8] (zero padded), mode 1 = bf16, 2 = fp16.  Supports zdiv == 1,
-// split == INT_MAX, dil > 0, K % 32 == 0, 0 <= pre_slope <= 1 and an epilogue of bias [+ residual]
-// [+ accumulate] only (the HiFi-GAN ResBlock convs).
+// split == INT_MAX, dil > 0, K % 32 == 0, 0 <= pre_slope <= 1 and one of two epilogues: bias [+ residual]
+// [+ accumulate] (the HiFi-GAN ResBlock convs; fp32 or 16-bit images in / out, mode 3 too), or with a->text_epi
+// (the text side's convs; modes 1 and 2, fp32 in and out) [bias], alpha, none / ReLU / GELU, [+ residual],
+// [length mask] — no accumulate, bvec, div, rmul, output stride or offset.  Anything else: -2, nothing launched.
+// M, N or nbatch <= 0: 0, nothing launched.
 extern "C" int cmtts_launch_conv16(const ConvArgs* ap, const void* wfrag, int mode, int nbatch, void* stream_) {
     const ConvArgs& a = *ap;
     hipStream_t stream = (hipStream_t)stream_;

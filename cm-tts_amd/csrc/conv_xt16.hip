@@ -7,6 +7,7 @@
 // Same conversions, same (32-channel chunk, tap, k-group) accumulation order and the same epilogue (conv_epilogue.h: bias, alpha, none / ReLU /
 // GELU, residual, length mask) as conv_mfma16.hip's text path => BITWISE equal to it (tests/test_gpu_parity.py::test_text16_xresident_bitwise).
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdlib.h>
 #include "conv_args.h"
 #include "conv_epilogue.h"
@@ -149,14 +150,16 @@ int dispatch_xt16(const ConvArgs& a, const void* wfrag, int nbatch, hipStream_t 
 int g_conv_xt16 = 1;      // internal switch "text_xt16": 0 = the chunked kernel for every text16 conv (same bits)
 
 // The text-side convs with K = 256 input channels (ConvArgs::text_epi), `wfrag` = to_fragment16 weights, mode 1 = bf16, 2 = fp16.
-// 0 = launched, -2 = shape not covered (cmtts_launch_conv16 then runs the chunked kernel: same bits), -3 = HIP error.
+// 0 = launched, -2 = not covered, nothing launched (cmtts_launch_conv16 then runs the chunked kernel: same bits; what is refused is listed in
+// conv_args.h), -3 = HIP error.  The kernel writes out[0] through epi_tile_simple alone: a second output (split) or a factor that epilogue does not
+// have (rmul) is refused, not ignored.
 extern "C" int cmtts_launch_conv_xt16(const ConvArgs* ap, const void* wfrag, int mode, int nbatch, void* stream_) {
     const ConvArgs& a = *ap;
-    if (!g_conv_xt16 || !a.text_epi || a.K != KC || a.M % 128 != 0 || a.dil != 1 || a.pad != (a.taps - 1) / 2 || a.pre_div != 1.f || a.pre_slope != 1.f || a.zdiv != 1 ||
-        a.x16 || a.y16 || (mode != 1 && mode != 2) || (long)a.K * a.ldx >= (1L << 31))
+    if (!g_conv_xt16 || !a.text_epi || a.M <= 0 || a.N <= 0 || nbatch <= 0 || a.K != KC || a.M % 128 != 0 || a.dil != 1 || a.pad != (a.taps - 1) / 2 ||
+        a.pre_div != 1.f || a.pre_slope != 1.f || a.zdiv != 1 || a.split != INT_MAX || a.x16 || a.y16 || (mode != 1 && mode != 2) || (long)a.K * a.ldx >= (1L << 31))
         return -2;
     const ConvOut& o = a.out[0];
-    if (o.ostride != 1 || o.ooff_base != 0 || o.ooff_mul != 0 || o.row_off != 0 || o.div != 1.0f || o.accum || o.bvec || o.Tout != a.N ||
+    if (o.ostride != 1 || o.ooff_base != 0 || o.ooff_mul != 0 || o.row_off != 0 || o.div != 1.0f || o.rmul != 0.0f || o.accum || o.bvec || o.Tout != a.N ||
         (o.act != ACT_NONE && o.act != ACT_RELU && o.act != ACT_GELU_ERF))
         return -2;
     return mode == 1 ? dispatch_xt16<1>(a, wfrag, nbatch, (hipStream_t)stream_) : dispatch_xt16<2>(a, wfrag, nbatch, (hipStream_t)stream_);

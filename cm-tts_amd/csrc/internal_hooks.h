@@ -96,7 +96,8 @@ int cmtts_internal_ge2e_mel_basis(float* out);
 // alone on the caller's device buffers, one hook per wrapper, cmtts_internal_k_<name>(<the wrapper's arguments in its order, defaulted ones
 // included>, stream).  NOTHING is validated: the arguments reach the wrapper unchanged, so the launch is production's (k_dense_small's 16-slice
 // rule, k_conv_post's 16-byte-load rule, k_durations wave against k_durations_serial).  Returns 0; -2 where a bool wrapper (k_ln_linear,
-// k_stats_mlp) declined, nothing launched.  The generic conv needs no hook: cmtts_launch_conv (conv_args.h) is exported.
+// k_stats_mlp) declined, nothing launched.  The generic conv needs no hook: cmtts_launch_conv (conv_args.h) is exported,
+// as are its 16-bit forms cmtts_launch_conv16 (the ResBlock epilogue, or with text_epi the text side's) and cmtts_launch_conv_xt16 (what each refuses: conv_args.h).
 // Bitwise contracts these tests hold: k_ln_linear_energy == k_ln_linear + k_energy_embed; k_stats_mlp == three k_dense_small launches;
 // conv_post_v4_kernel == conv_post_kernel; durations wave == serial; a durations table of one value == the scalar form.
 int cmtts_internal_k_embed_tokens(const int64_t* texts, const int64_t* lens, const float* E, const float* omega, const float* tab, int tab_rows,

@@ -1864,7 +1864,9 @@ def test_ragged_text_batch_bitwise():
 def test_text16_xresident_bitwise(variant, B, L, dtype):
     """conv_xt16.hip (the text16 convs with 256 input channels: whole x^T tile of an utterance staged once, hand-issued weight ring, no barrier
     in the K loop) keeps conv_mfma16.hip's conversions, (chunk, tap, k-group) order and epilogue: every output of the text side — floats and
-    integers — must not change by a bit.  L = 85 / 31 / 1: one ragged 96-column tile; 170: two tiles; ragged lengths exercise the masks."""
+    integers — must not change by a bit.  L = 85 / 31 / 1: one ragged 96-column tile; 170: two tiles; ragged lengths exercise the masks.
+    Kernel against kernel through whole models: an error both share passes here.  The element-wise anchor — each launch alone against float64,
+    and the two kernels bit for bit on both sides of every tile edge — is tests/test_gpu_text16_kernels.py."""
     host = _host()
     cfg = get_config(variant)
     model = host.CMTotalTTS(cfg, DEV).load_state_dict(synth_cmtts_state_dict(cfg, seed=31, dur_frames=4.0, dur_spread=0.03))
